@@ -3,7 +3,13 @@
 (BASELINE.json configs[2]: 2^20 points x random 252-bit scalars per GPU) on N MI355X.
 
     python bench.py --gpus 1 --steps K --warmup W          (defaults: K = 20, W = 5 -- the driver's own invocation)
+    python bench.py --gpus 1 --steps K --warmup W --full   (+ roofline, CPU baseline, oracle parity check, secondary configs)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the result line.  Its
+`roofline`, `cpu_baseline` and `parity_spot_check` are null; everything described below under roofline, cpu_baseline,
+parity and `secondary` is measured and checked with `--full`.
 
 A "step" is one pass of zc_ed_scalar_mul (strict mode: the reference's formula sequence,
 bit-identical (X:Y:Z:T) limbs) over the rank's 2^20 HBM-resident points and scalars.
@@ -13,12 +19,17 @@ Independent elements: the batch is sharded across ranks with no data-path collec
 partial sums inside the library, ordered fold on the device.  `--workload ecdh` is the reference's only
 macro-benchmark (benchmarks/dusk_benchmarks.rs:544-620): two key generations and two shared secrets per unit.
 PyTorch supplies device memory, the stream and torch.distributed; all arithmetic is in
-libzerocaf_hip.so.  The oracle (oracle/) is touched only after the timed region: the
+libzerocaf_hip.so.  The oracle (oracle/) is touched only with `--full`, after the timed region: the
 cpu_baseline leg (the same operation on the host cores) whose results double as the parity
 spot check of the GPU output (`--cpu-sample 0` skips both).
 Prints ONE JSON line on rank 0.
 
-The default single-GPU run (the driver's) also carries `secondary`: the other BASELINE configs -- fe_mul 2^24 and
+`--dump-outputs DIR` (rank 0, after the timed steps): what the last timed step returned to its caller, one DIR/<name>.npy
+per output array.  64-bit limbs as float64 with a trailing axis of 2 (low 32 bits, high 32 bits: exact), bytes and ok
+masks as float32.  Arrays with one row per unit keep at most DUMP_ROWS rows, the fixed sample spread_sample(n, DUMP_ROWS)
+whose unit indices are DIR/rows.npy.  The inputs are seeded, so two builds can be compared output for output.
+
+The default single-GPU run with `--full` also carries `secondary`: the other BASELINE configs -- fe_mul 2^24 and
 fe_invert 2^20 (configs[1]), the Ristretto round trip 2^22 (configs[3]), the MSM shard 2^21 (configs[4]) -- and the ECDH
 exchange, a few steps each AFTER the headline's timed region and outside its ms_per_step, each with its own roofline
 record and oracle spot check (`--no-secondary` skips them).
@@ -248,19 +259,22 @@ def make_run(env, wl, n, scalar_bits, mode="strict", ecdh="wire"):
 
 
 def time_run(env, run, steps, warmup):
-    """W untimed steps, then exactly K steps bracketed by barrier + synchronize; HIP events on the launch stream per step."""
+    """W untimed steps, then exactly K steps bracketed by barrier + synchronize; HIP events on the launch stream per step.
+    What the last timed step returned is kept as run["last"] (--dump-outputs)."""
     torch = env.torch
     for _ in range(warmup):
         run["step"]()
     env.barrier()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    last = None
     t0 = time.perf_counter()
     for i in range(steps):
         ev[i][0].record(env.stream)
-        run["step"]()
+        last = run["step"]()
         ev[i][1].record(env.stream)
     env.barrier()
     dt = time.perf_counter() - t0
+    run["last"] = last
     if env.world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         env.dist.all_reduce(t, op=env.dist.ReduceOp.MAX)
@@ -452,6 +466,52 @@ def spread_sample(n, m, seed=SAMPLE_SEED):
 def take_rows(env, t, idx):
     """rows idx of a device tensor, on the host"""
     return t.index_select(0, env.torch.from_numpy(idx).to(t.device)).cpu().numpy()
+
+
+DUMP_ROWS = 1 << 15              # --dump-outputs: rows kept per per-unit array (the ECDH reference variant's four point arrays: 42 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(run):
+    """What a caller of the timed path received from its last step, by name (device tensors or host arrays)."""
+    wl, st, last = run["wl"], run["st"], run.get("last")
+    if wl == "scalar_mul":
+        return {"points": st["out"]}
+    if wl == "fe_mul":
+        return {"product": last}
+    if wl == "fe_invert":
+        return {"inverse": last[0], "ok": last[1]}
+    if wl == "ristretto":
+        return {"encodings": st["out"], "ok": st["ok"]}
+    if wl == "msm":
+        return {"sum": st["result"]}
+    names = ("A", "Bp", "S", "Sp", "ok1", "ok2") if run["ecdh"] == "wire" else ("A", "Bp", "S", "Sp")
+    return {k: st[k] for k in names}
+
+
+def dump_arrays(outputs, n, out_dir):
+    """Write each output as out_dir/<name>.npy (float32 / float64, see the module doc); per-unit arrays (n rows) are cut to the
+    fixed sample spread_sample(n, DUMP_ROWS), recorded as out_dir/rows.npy.  `outputs`: name -> host array or device tensor."""
+    idx = spread_sample(n, DUMP_ROWS)
+    files = {"rows": idx.astype(np.float64)}
+    for name, a in outputs.items():
+        if not isinstance(a, np.ndarray):             # a device tensor
+            import torch
+            a = (a.index_select(0, torch.from_numpy(idx).to(a.device)) if a.shape[0] == n else a).cpu().numpy()
+        elif a.shape[0] == n:
+            a = a[idx]
+        if a.dtype.itemsize == 8:
+            u = np.ascontiguousarray(a).view(np.uint64)
+            files[name] = np.stack([u & np.uint64(0xFFFFFFFF), u >> np.uint64(32)], axis=-1).astype(np.float64)
+        else:
+            files[name] = a.astype(np.float32)
+    total = sum(x.nbytes for x in files.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    return sorted(files)
 
 
 def cpu_leg(env, run, sample):
@@ -762,11 +822,18 @@ def main():
                     help="ecdh only: wire = public keys and shared secrets as 32-byte Ristretto encodings (comb key generation, fused "
                          "round trips); reference = the reference's ecdh_double_add literally (four strict double_and_add calls)")
     ap.add_argument("--cpu-sample", type=int, default=-1, help="units for the CPU baseline / parity check (0 disables)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other configs' lines in the default single-GPU run")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the other configs' lines in the default single-GPU --full run")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: roofline (with the live multiplier-rate ubench), CPU baseline and oracle parity spot "
+                         "check, the MSM fold check and, in the default single-GPU config, the secondary configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0; see the module doc)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return self_launch(args, json_fd)            # plain `python bench.py --gpus N`: launch the N ranks ourselves
 
@@ -805,6 +872,8 @@ def main():
 
     run = make_run(env, wl, n, args.scalar_bits, args.mode, args.ecdh)
     dt, kern_avg_s = time_run(env, run, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_arrays(step_outputs(run), n, args.dump_outputs)
 
     # what makes a multi-GPU line self-proving: which physical device every rank ran on (N distinct ones), the rank
     # count RCCL itself reports for the library's communicator, and every rank's own kernel time (a straggler shows)
@@ -828,7 +897,7 @@ def main():
         raise SystemExit("bench.py: the library's RCCL communicator does not span %d ranks: %s" % (world, idents))
 
     msm_fold_ok = None
-    if wl == "msm" and args.cpu_sample != 0:                 # --cpu-sample 0 skips every parity check (profiling runs)
+    if args.full and wl == "msm" and args.cpu_sample != 0:   # --cpu-sample 0 skips every parity check (profiling runs)
         msm_fold_ok = msm_fold_check(env, run)
 
     if rank != 0:
@@ -839,10 +908,10 @@ def main():
     W = WORKLOADS[wl]
     units = n * world * args.steps
     value = units / dt
-    roofline = roofline_for(env, run, kern_avg_s)
+    roofline = roofline_for(env, run, kern_avg_s) if args.full else None
 
     cpu, checked = None, None
-    sample = args.cpu_sample
+    sample = args.cpu_sample if args.full else 0
     baseline_leg = world == 1 or sample > 0         # the CPU baseline is reported at N = 1 (or when asked for)
     if sample < 0:
         from oracle import zc_ref as _z
@@ -851,7 +920,7 @@ def main():
         checked, cpu = check_and_baseline(env, run, sample, baseline_leg, msm_fold_ok)
 
     secondary = None
-    if headline_default and world == 1 and not args.no_secondary and args.cpu_sample != 0:
+    if args.full and headline_default and world == 1 and not args.no_secondary and args.cpu_sample != 0:
         del run
         torch.cuda.empty_cache()
         secondary = secondary_runs(env)
@@ -865,7 +934,7 @@ def main():
               "ecdh": "ECDH exchanges/sec (two key generations + two shared secrets each; the reference's macro-benchmark)"}[wl]
     line = {
         "metric": metric, "value": round(value, 1), "unit": W["unit"],
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": round(dt / args.steps * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u64 (nine 29-bit limbs in u32 registers, 64-bit multiply-accumulate columns)", "data": "synthetic",

@@ -1,5 +1,5 @@
 """GPU tier: bench.py's output contract -- exactly ONE JSON line on stdout with the fields the driver
-reads, `roofline` and `cpu_baseline` objects, the parity check passed -- for one rank, and for two ranks
+reads; with --full `roofline` and `cpu_baseline` objects and the parity check passed -- for one rank, and for two ranks
 launched the way the driver launches them (torch.distributed.run, 127.0.0.1).  A one-GPU box cannot give
 each rank its own device, so the two-rank runs use bench.py's test hooks: both ranks on device 0 and
 gloo for the barrier / MAX-reduce (RCCL refuses two ranks on one device)."""
@@ -57,9 +57,77 @@ def test_spot_check_sample_covers_head_tail_and_a_stride_through_the_middle():
     assert np.array_equal(bench.spread_sample(100, 100), np.arange(100)) and np.array_equal(bench.spread_sample(100, 1000), np.arange(100))
 
 
+def test_dump_arrays_are_exact_floats_of_a_fixed_sample(tmp_path):
+    """--dump-outputs' writer: 64-bit limbs as float64 (low, high 32-bit halves: exact over the whole range), byte arrays as
+    float32, per-unit arrays cut to the fixed spread_sample of DUMP_ROWS rows (recorded as rows.npy), others kept whole;
+    small batches whole; more than 64 MB refused before anything is written."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 3 * bench.DUMP_ROWS + 5
+    rng = np.random.default_rng(3)
+    limbs = rng.integers(0, 1 << 64, size=(n, 20), dtype=np.uint64)
+    ok = rng.integers(0, 2, size=n, dtype=np.uint8)
+    one = limbs[:1].copy()
+    d = tmp_path / "d"
+    assert bench.dump_arrays({"points": limbs, "ok": ok, "sum": one}, n, str(d)) == ["ok", "points", "rows", "sum"]
+    f = {k: np.load(d / (k + ".npy")) for k in ("ok", "points", "rows", "sum")}
+    idx = bench.spread_sample(n, bench.DUMP_ROWS)
+    join = lambda a: a[..., 0].astype(np.uint64) | (a[..., 1].astype(np.uint64) << np.uint64(32))
+    assert f["rows"].dtype == np.float64 and np.array_equal(f["rows"].astype(np.int64), idx)
+    assert f["points"].dtype == np.float64 and f["points"].shape == (bench.DUMP_ROWS, 20, 2) and np.array_equal(join(f["points"]), limbs[idx])
+    assert f["ok"].dtype == np.float32 and np.array_equal(f["ok"], ok[idx])
+    assert f["sum"].shape == (1, 20, 2) and np.array_equal(join(f["sum"]), one)
+    small = tmp_path / "small"
+    bench.dump_arrays({"x": limbs[:100]}, 100, str(small))
+    assert np.array_equal(np.load(small / "rows.npy"), np.arange(100)) and np.array_equal(join(np.load(small / "x.npy")), limbs[:100])
+    big = np.zeros((bench.DUMP_ROWS, 130), dtype=np.uint64)
+    with pytest.raises(SystemExit):
+        bench.dump_arrays({"x": big}, bench.DUMP_ROWS, str(tmp_path / "big"))
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path, oracle):
+    """Without --full: the timed steps and the line, none of roofline, CPU baseline, parity check or secondary configs.
+    --dump-outputs: the last timed step's points, identical on a second run, and the oracle's on the seeded inputs."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 1 << 16
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--units", str(n),
+                              "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = _one_json_line(out.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["ms_per_step"] > 0
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity_spot_check"] is None and "secondary" not in d
+        assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+        dumps.append({p.stem: np.load(p) for p in out_dir.glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["points", "rows"] and all(np.array_equal(a[k], b[k]) for k in a)
+    idx = bench.spread_sample(n, bench.DUMP_ROWS)
+    assert np.array_equal(a["rows"].astype(np.int64), idx) and a["points"].shape == (bench.DUMP_ROWS, 20, 2)
+    got = a["points"][..., 0].astype(np.uint64) | (a["points"][..., 1].astype(np.uint64) << np.uint64(32))
+    # the same seeded inputs, made by bench.py's own make_run in this process; the oracle on every 64th dumped row
+    import torch
+    import dusk_zerocaf_amd as z
+    eng = z.Engine([0])
+    try:
+        run = bench.make_run(bench.Env(torch, z, eng, torch.cuda.current_stream(), 0, 1, "nccl", None), "scalar_mul", n, 252)
+        torch.cuda.synchronize()
+        sel = idx[::64]
+        P = run["data"]["P"].cpu().numpy().view(np.uint64)[sel]
+        assert np.array_equal(got[::64], oracle.ed_scalar_mul(P, run["data"]["host_K"][sel]))
+    finally:
+        eng.close()
+
+
 @pytest.mark.gpu
 def test_single_rank_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "4096"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-sample", "4096"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _one_json_line(out.stdout)
@@ -74,7 +142,7 @@ def test_single_rank_line():
     assert d["distinct_devices"] == 1 and len(d["devices"]) == 1 and d["devices"][0]["pci"]
     assert d["config"]["units_per_gpu_per_step"] == 1 << 20 and abs(d["value"] - (1 << 20) / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
     assert d["config"]["workload"].startswith("2^20 ") and r["schema"] == "useful-work/2" and "-march=" in c["sample"]
-    # the default single-GPU line carries the other BASELINE configs (and the reference's ECDH macro-benchmark) as `secondary`:
+    # the default single-GPU --full line carries the other BASELINE configs (and the reference's ECDH macro-benchmark) as `secondary`:
     # driver-box numbers for every config, each with its own roofline record and oracle spot check, outside the headline's timing
     sec = {x["name"]: x for x in d["secondary"]}
     assert list(sec) == ["fe_mul", "fe_invert", "ristretto", "msm", "ecdh", "scalar_mul_s249"]
@@ -110,12 +178,12 @@ def test_single_rank_line():
 @pytest.mark.gpu
 def test_workload_string_names_the_size_it_ran_at():
     """`config.workload` is derived from --units (a record of a 2^18-unit run must not say 2^20); other sizes carry no `secondary`."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--units", str(1 << 18), "--cpu-sample", "2048"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--units", str(1 << 18), "--cpu-sample", "2048"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _one_json_line(out.stdout)
     assert d["config"]["workload"].startswith("2^18 ") and d["config"]["units_per_gpu_per_step"] == 1 << 18 and "secondary" not in d
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--units", "300000", "--workload", "fe_mul", "--cpu-sample", "4096"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--units", "300000", "--workload", "fe_mul", "--cpu-sample", "4096"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     assert _one_json_line(out.stdout)["config"]["workload"].startswith("300000 ")
@@ -127,7 +195,7 @@ def test_ecdh_workload(variant):
     """The reference's macro-benchmark (benchmarks/dusk_benchmarks.rs:544-620): two key generations and two shared secrets per
     unit.  `wire`: 32-byte Ristretto encodings, equal to compress() of the oracle's ecdh_double_add key pairs and secrets;
     `reference`: the four double_and_add calls literally, limb-exact.  S == S' on every element either way (bench.py aborts otherwise)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "ecdh", "--ecdh", variant, "--units", str(1 << 16), "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "ecdh", "--ecdh", variant, "--units", str(1 << 16), "--steps", "2",
                           "--warmup", "1", "--cpu-sample", "1024"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _one_json_line(out.stdout)
@@ -140,7 +208,7 @@ def test_ecdh_workload(variant):
 def test_two_ranks_launched_like_the_driver(workload, units):
     env = dict(os.environ, ZC_BENCH_BACKEND="gloo", ZC_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--workload", workload, "--units", str(units)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -165,7 +233,7 @@ def test_plain_python_launch_starts_the_ranks_itself():
     # a rendezvous left over in the caller's environment is not trusted (an unroutable address, a privileged port): the ranks get
     # 127.0.0.1 and a free port unless ZC_BENCH_MASTER_ADDR / ZC_BENCH_MASTER_PORT say otherwise
     env.update(ZC_BENCH_BACKEND="gloo", ZC_BENCH_DEVICE="0", MASTER_ADDR="203.0.113.1", MASTER_PORT="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--units", str(1 << 18)],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--units", str(1 << 18)],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_json_line(out.stdout)
@@ -206,7 +274,7 @@ def test_gpus_flag_fails_closed_without_a_gpu():
 @pytest.mark.gpu
 def test_msm_line_reports_the_library_communicator():
     """One rank, the real in-library RCCL path: ncclCommCount of the context's communicator is on the line."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "msm", "--units", str(1 << 16), "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "msm", "--units", str(1 << 16), "--steps", "2",
                           "--warmup", "1", "--cpu-sample", "2048"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _one_json_line(out.stdout)

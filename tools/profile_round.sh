@@ -32,24 +32,24 @@ tools/profile_pmc.sh "$TAG" > "$OUT/pmc.log" 2>&1
 [ -x tools/ubench/occupancy ] && timeout 300 tools/ubench/occupancy 20 > "$OUT/occupancy.txt" 2>&1
 fi
 cd "$REPO"
-python bench.py > "$OUT/bench_scalar_mul.json" 2> "$OUT/bench_scalar_mul.log"
-python bench.py --scalar-bits 249 --cpu-sample 0 > "$OUT/bench_scalar_mul_s249.json" 2>/dev/null
-python bench.py --units 16777216 --steps 3 --warmup 1 --cpu-sample 0 > "$OUT/bench_scalar_mul_2p24.json" 2>/dev/null
-python bench.py --mode fast > "$OUT/bench_scalar_mul_fast.json" 2>/dev/null
-python bench.py --workload ristretto > "$OUT/bench_ristretto_2p20.json" 2>/dev/null
-python bench.py --workload ristretto --units 4194304 --steps 3 --warmup 1 > "$OUT/bench_ristretto_2p22.json" 2>/dev/null
-python bench.py --workload fe_mul > "$OUT/bench_fe_mul_2p20.json" 2>/dev/null
-python bench.py --workload fe_mul --units 16777216 --steps 20 --warmup 30 --cpu-sample 0 > "$OUT/bench_fe_mul_2p24.json" 2>/dev/null
-python bench.py --workload fe_invert > "$OUT/bench_fe_invert_2p20.json" 2>/dev/null
-python bench.py --workload fe_invert --units 16777216 --steps 10 --warmup 5 --cpu-sample 65536 > "$OUT/bench_fe_invert_2p24.json" 2>/dev/null
-python bench.py --workload msm > "$OUT/bench_msm_2p20.json" 2>/dev/null
-python bench.py --workload msm --units 2097152 > "$OUT/bench_msm_2p21.json" 2>/dev/null
-python bench.py --workload msm --units 16777216 --steps 3 --warmup 1 > "$OUT/bench_msm_2p24.json" 2>/dev/null
+python bench.py --full > "$OUT/bench_scalar_mul.json" 2> "$OUT/bench_scalar_mul.log"
+python bench.py --full --scalar-bits 249 --cpu-sample 0 > "$OUT/bench_scalar_mul_s249.json" 2>/dev/null
+python bench.py --full --units 16777216 --steps 3 --warmup 1 --cpu-sample 0 > "$OUT/bench_scalar_mul_2p24.json" 2>/dev/null
+python bench.py --full --mode fast > "$OUT/bench_scalar_mul_fast.json" 2>/dev/null
+python bench.py --full --workload ristretto > "$OUT/bench_ristretto_2p20.json" 2>/dev/null
+python bench.py --full --workload ristretto --units 4194304 --steps 3 --warmup 1 > "$OUT/bench_ristretto_2p22.json" 2>/dev/null
+python bench.py --full --workload fe_mul > "$OUT/bench_fe_mul_2p20.json" 2>/dev/null
+python bench.py --full --workload fe_mul --units 16777216 --steps 20 --warmup 30 --cpu-sample 0 > "$OUT/bench_fe_mul_2p24.json" 2>/dev/null
+python bench.py --full --workload fe_invert > "$OUT/bench_fe_invert_2p20.json" 2>/dev/null
+python bench.py --full --workload fe_invert --units 16777216 --steps 10 --warmup 5 --cpu-sample 65536 > "$OUT/bench_fe_invert_2p24.json" 2>/dev/null
+python bench.py --full --workload msm > "$OUT/bench_msm_2p20.json" 2>/dev/null
+python bench.py --full --workload msm --units 2097152 > "$OUT/bench_msm_2p21.json" 2>/dev/null
+python bench.py --full --workload msm --units 16777216 --steps 3 --warmup 1 > "$OUT/bench_msm_2p24.json" 2>/dev/null
 python tools/bench_ops.py fe_add,fe_neg,fe_mul,fe_square 16777216 10 > "$OUT/ops.txt" 2>/dev/null
 python tools/bench_ops.py fe_invert,fe_div,fe_sqrt_ratio_i,ed_add,ed_double,ed_neg,ed_eq,ris_eq,ed_is_valid,ed_compress,ed_decompress,ris_compress,ris_decompress,ed_to_affine 1048576 10 >> "$OUT/ops.txt" 2>/dev/null
 python tools/bench_ops.py ed_mul_base,ris_mul_base_compress,ed_mul_base_wnaf5 4194304 5 >> "$OUT/ops.txt" 2>/dev/null
-python bench.py --workload ecdh > "$OUT/bench_ecdh_2p20.json" 2>/dev/null
-python bench.py --workload ecdh --ecdh reference --steps 5 --warmup 2 > "$OUT/bench_ecdh_reference_2p20.json" 2>/dev/null
+python bench.py --full --workload ecdh > "$OUT/bench_ecdh_2p20.json" 2>/dev/null
+python bench.py --full --workload ecdh --ecdh reference --steps 5 --warmup 2 > "$OUT/bench_ecdh_reference_2p20.json" 2>/dev/null
 python tools/host_path.py 20 2>/dev/null | grep '"auto"\|"1"\|slots' > "$OUT/host_path.txt"
 python tools/host_path.py 22 2>/dev/null | grep '"auto"\|"1"\|slots' >> "$OUT/host_path.txt"
 ls -la "$OUT"

@@ -104,20 +104,25 @@ ZC_DI u32 scalar_bits(const u64 (&l)[5], int bit, int c)
     return (u32)x & (u32)(((u64)1 << c) - 1);
 }
 
-ZC_KERNEL void k_msm_digits(const u64* k, u32* keys, size_t n, int c, int W)
+// the W digit words of one scalar, word w at keys[w * stride]
+ZC_DI void msm_digit_keys(const u64* __restrict__ k, u32* __restrict__ keys, size_t stride, int c, int W)
 {
-    const size_t i = gid();
-    if (i >= n) return;
     u64 l[5];
-    load_scalar(l, k + 5 * i);
+    load_scalar(l, k);
     const u32 half = 1u << (c - 1);
     u32 carry = 0;
     for (int w = 0; w < W; w++) {
         const u32 raw = scalar_bits(l, w * c, c) + carry;              // 0 .. 2^c
         carry = raw > half ? 1u : 0u;                                    // digit = raw - carry * 2^c
         const u32 mag = carry ? (1u << c) - raw : raw;                   // |digit| in 0 .. 2^(c-1)
-        keys[(size_t)w * n + i] = (mag ? mag - 1 : half) | (carry << 31);
+        keys[(size_t)w * stride] = (mag ? mag - 1 : half) | (carry << 31);
     }
+}
+ZC_KERNEL void k_msm_digits(const u64* k, u32* keys, size_t n, int c, int W)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    msm_digit_keys(k + 5 * i, keys + i, n, c, W);
 }
 
 // Cached ("projective Niels") form of an input point for the bucket sums: (Y-X, Y+X, Z, 2dT),
@@ -818,6 +823,31 @@ ZC_KERNEL void k_msm_shift(const u64* in, u64* out, int k)
     if (!msm_is_literal_identity(in))
         for (int i = 0; i < k; i++) Q = pt_double_quad(Q, role);
     if (threadIdx.x == 0) pt_store(out, Q);
+}
+
+// ---------------------------------------------------------------- fixed bases (zc_msm_bases_create / zc_msm_fixed)
+// A table of n bases holds W = ceil(261 / c) windows of affine records (k_msm_prepare_affine, 128-byte stride): record j n + i
+// is 2^(c j) P_i.  One scalar vector's W n digits then name W n distinct records, so the vector is ONE window of the key sort
+// and its bucket sums are its result: no doublings, no Horner's rule, no per-call normalisation.
+// Window j of the table from window j - 1: c doublings per point (the squaring form of the reference's Double; the records
+// only need the group element).  Plain coordinates in and out, as k_ed_double.
+ZC_KERNEL void k_msm_fixed_double(const u64* in, u64* out, size_t n, int c)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    pt a = pt_load_plain(in + 20 * i);
+    for (int k = 0; k < c; k++) a = pt_double_plain(a);
+    pt_store_plain(out + 20 * i, a);
+}
+// Digits of `batch` scalar vectors of n scalars each (batch-major, scalar b n + i) in ONE launch, the recoding of k_msm_digits:
+// vector b is sort window b of n W entries, its digit of window j for scalar i at keys[b n W + j n + i] -- the in-window
+// index j n + i is the table record of 2^(c j) P_i.
+ZC_KERNEL void k_msm_fixed_digits(const u64* k, u32* keys, size_t n, size_t batch, int c, int W)
+{
+    const size_t g = gid();
+    if (g >= n * batch) return;
+    const size_t b = g / n, i = g - b * n;
+    msm_digit_keys(k + 5 * g, keys + b * n * (size_t)W + i, n, c, W);
 }
 
 }  // namespace zc

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -176,11 +178,21 @@ struct RcclApi {
     const char* (*GetErrorString)(ncclResult_t) = nullptr;
 };
 
+// A fixed-base MSM table (zc_msm_bases_create): W windows of n affine records, its own allocation on device slot `slot`.
+struct MsmBases {
+    int slot = 0;
+    void* recs = nullptr;
+    size_t n = 0, bytes = 0;
+    int c = 0, W = 0;
+};
+std::atomic<uint64_t> g_next_bases_id{1};   // table ids: nonzero, process-wide, never reused
+
 }  // namespace
 
 struct zc_ctx {
     std::vector<DevState> devs;
     std::mutex mu;
+    std::map<uint64_t, MsmBases> bases;   // live fixed-base tables by id (ids come from one process-wide counter: never reused)
     ncclComm_t comm = nullptr;          // zc_comm_init: one rank per process, device 0 of the context
     int rank = 0, world = 1;
 };
@@ -813,6 +825,163 @@ MsmPlan msm_plan(size_t cnt, bool points_aligned16, const Tuning& tune)
     return p;
 }
 
+// ---------------------------------------------------------------- fixed-base MSM plan (zc_msm_bases_create / zc_msm_fixed)
+// Window width of a table of n bases: per scalar vector the bucket sums cost n W additions and the reduction about 3.7 per
+// bucket (the figure behind msm_window_bits), 2^(c-1) buckets: c minimises n ceil(261 / c) + 3.7 2^(c-1).  There is no
+// doubling chain to hide, and c is fixed when the table is built.
+int msm_fixed_window_bits(size_t n)
+{
+    int best = zc::MSM_MIN_C;
+    double best_cost = 0;
+    for (int c = zc::MSM_MIN_C; c <= zc::MSM_MAX_C; c++) {
+        const double cost = (double)n * (double)((zc::MSM_SCALAR_BITS + c - 1) / c) + 3.7 * (double)((size_t)1 << (c - 1));
+        if (c == zc::MSM_MIN_C || cost < best_cost) best = c, best_cost = cost;
+    }
+    return best;
+}
+// One window group (G = 1) whose "windows" are the batch's scalar vectors: each is a sort window of n W entries.
+struct MsmFixedPlan {
+    int c = 0, W = 0;
+    size_t m = 0, nb = 0;          // list entries (batch n W), buckets (batch 2^(c-1))
+    int T = 0, TE = 8, seg = 0;    // run lengths (level 0, deeper levels), buckets per reduction segment
+    size_t nseg = 0, nl0 = 0;      // segments, level-0 lanes
+    MsmSortPlan sort;
+};
+MsmFixedPlan msm_fixed_plan(size_t n, int c, size_t batch, const Tuning& tune)
+{
+    MsmFixedPlan p;
+    p.c = c;
+    p.W = (zc::MSM_SCALAR_BITS + c - 1) / c;
+    p.m = batch * n * (size_t)p.W;
+    p.nb = batch << (c - 1);
+    p.sort = msm_sort_plan(n * (size_t)p.W, c, (int)std::min<size_t>(batch, 0x7FFFFFFF), tune);
+    p.T = msm_run_length(p.m, tune);
+    if (tune.msm_run_edges) p.TE = tune.msm_run_edges & ~1;
+    p.seg = tune.msm_seg ? tune.msm_seg : zc::msm_segment_buckets(p.nb);
+    while (p.seg > (1 << (c - 1))) p.seg >>= 1;           // a segment never spans windows
+    p.nseg = p.nb / (size_t)p.seg;
+    p.nl0 = (p.m + (size_t)p.T - 1) / (size_t)p.T;
+    return p;
+}
+// window_bits 0 / 5..22 and the index limits of a table of n bases, checked before anything is allocated
+int msm_fixed_check(size_t n, int window_bits, int* c_out, int* W_out, const char* who)
+{
+    char msg[160];
+    if (n == 0) return snprintf(msg, sizeof msg, "%s: no bases", who), fail(ZC_ERR_BAD_ARG, msg);
+    if (window_bits != 0 && (window_bits < zc::MSM_MIN_C || window_bits > zc::MSM_MAX_C))
+        return snprintf(msg, sizeof msg, "%s: window_bits %d outside 0 or %d..%d", who, window_bits, zc::MSM_MIN_C, zc::MSM_MAX_C), fail(ZC_ERR_BAD_ARG, msg);
+    const int c = window_bits ? window_bits : msm_fixed_window_bits(n);
+    const int W = (zc::MSM_SCALAR_BITS + c - 1) / c;
+    if (n >= ((size_t)1 << 31) / (size_t)W + 1 || n * (size_t)W >= ((size_t)1 << 31))
+        return snprintf(msg, sizeof msg, "%s: %zu bases x %d windows do not fit 31-bit record indices", who, n, W), fail(ZC_ERR_BAD_ARG, msg);
+    *c_out = c;
+    *W_out = W;
+    return ZC_OK;
+}
+
+// The affine normalisation of cnt points (16-byte aligned) into records of rec_words words, on stream `st`.
+// Points per lane: a CU holds twelve of its one-wave workgroups (LDS), so 2^17 lanes = 2048 waves are one round of resident
+// waves with room left for the key sort beside them, and 8 - 16 points amortise the lane's inversion (round 6, prefetching
+// kernel: 2^20 pairs 4 -> 8 per lane 2.30 -> 2.26 ms, 2^21 8 -> 16 3.34 -> 3.31, flat from 10 to 16; ZC_MSM_AFFINE_CHUNK overrides)
+void msm_prepare_affine(hipStream_t st, const u64* dP, zc::u32* recs, size_t cnt, const Tuning& tune, zc::u32 rec_words)
+{
+    int ac = (int)std::min<size_t>(16, std::max<size_t>(1, cnt >> 17));
+    if (tune.msm_affine_chunk) ac = tune.msm_affine_chunk;
+    const size_t lanes = (cnt + ac - 1) / ac;                // lane g owns points g, g + stride, ...: stride = the launch's lanes
+    hipLaunchKernelGGL(zc::k_msm_prepare_affine, dim3((unsigned)((lanes + zc::MSM_PREP_BLOCK - 1) / zc::MSM_PREP_BLOCK)), dim3(zc::MSM_PREP_BLOCK), 0, st, dP, recs, cnt, ac, rec_words);
+}
+
+// The buffers of the bucket sums and their reduction: the lower half of the bucket method, shared by zc_msm (msm_on_device)
+// and zc_msm_fixed.
+struct MsmReduceBufs {
+    const uint2* sorted;                  // the key sort's pairs (bucket key, record index | sign << 31)
+    const zc::u32* recs;                  // the cached records the pairs name
+    zc::u32 rec_words;                    // their stride in 32-bit words
+    bool affine;                          // affine records (7-multiplication additions), else projective
+    size_t m, nb;                         // list entries, buckets
+    zc::u32* buckets;
+    uint8_t* present;                     // one flag per bucket, zeroed by the caller
+    zc::u32* ekeys[2];                    // edge lists of the segmented reduction, ping-pong
+    zc::u32* erecs[2];
+    int c, TE;                            // window bits, run length of the deeper levels
+};
+// The windows [w0, w0 + nw): the level-0 bucket sums on D.s() (lanes [slot0, slot0 + nl0) of the edge arrays, over the list part
+// [*range_lo, *range_end) or, with null range pointers, the whole list), then on `st` -- behind the event `go`, recorded here, when
+// that is another stream -- the deeper levels of the segmented reduction, the segment sums (nsegg segments of `seg` buckets, four
+// lanes per segment up to quad_max of them) and the folds down to one point per window.  *sums: the nw window sums (seg_out or fold_b).
+int msm_reduce_windows(DevState& D, const MsmReduceBufs& rb, int w0, int nw, int T, size_t nl0, size_t slot0, const zc::u32* range_lo,
+                       const zc::u32* range_end, size_t pad, hipStream_t st, hipEvent_t go, int seg, size_t nsegg, size_t quad_max, u64* seg_out,
+                       u64* fold_b, u64** sums)
+{
+    const int c = rb.c, TE = rb.TE;
+    const size_t m = rb.m, nb = rb.nb;
+    zc::u32* const buckets = rb.buckets;
+    uint8_t* const present = rb.present;
+    zc::u32* const* ekeys = rb.ekeys;
+    zc::u32* const* erecs = rb.erecs;
+    const size_t b0 = (size_t)w0 << (c - 1);                          // the windows' first bucket
+    hipLaunchKernelGGL(rb.affine ? zc::k_msm_runs_affine : zc::k_msm_runs, dim3((unsigned)((nl0 + zc::MSM_RUN_BLOCK - 1) / zc::MSM_RUN_BLOCK)), dim3(zc::MSM_RUN_BLOCK), pad,
+                       D.s(), rb.sorted, rb.recs, (zc::u32)m, (zc::u32)T, (zc::u32)nb, buckets, present, ekeys[0], erecs[0], range_lo, range_end,
+                       (zc::u32)nl0, (zc::u32)slot0, rb.rec_words);
+    if (st != D.s()) {
+        HIP_TRY(hipEventRecord(go, D.s()));
+        HIP_TRY(hipStreamWaitEvent(st, go, 0));
+    }
+    // deeper levels of the segmented reduction: the edge list of the level above, level by level, in short runs (a bucket
+    // cut once closes at level 1: nearly every edge of a uniform batch; the levels behind it find sentinel keys only and
+    // take 5 us each.  Runs of 64 there -- 5 launches instead of 9 -- were measured: a lane then walks 64 sentinel keys
+    // one dependent load after the other, 340 us per level instead of 5).
+    {
+        const zc::u32* lk = ekeys[0] + 2 * slot0;
+        const zc::u32* lr = erecs[0] + 2 * slot0 * zc::MSM_RAW_WORDS;
+        size_t len = 2 * nl0;
+        for (int level = 1; nl0 > 1; level++) {
+            // runs shifted by one entry, [jT+1, (j+1)T+1), run 0 one longer
+            const size_t t = (size_t)TE;
+            const size_t nl = len <= t + 1 ? 1 : (len - 1 + t - 1) / t;
+            zc::u32* nk = ekeys[level & 1] + 2 * slot0;
+            zc::u32* nr = erecs[level & 1] + 2 * slot0 * zc::MSM_RAW_WORDS;
+            if (nl <= (size_t)ZC_MSM_EDGES_QUAD)       // four lanes per run: the level is a few dependent additions on a fraction of the chip
+                hipLaunchKernelGGL(zc::k_msm_runs_edges_quad, dim3(grid_for(4 * nl)), dim3(zc::ZC_BLOCK), 0, st, lk, lr, (zc::u32)len, (zc::u32)t, (zc::u32)nb,
+                                   buckets, present, nk, nr);
+            else
+                hipLaunchKernelGGL(zc::k_msm_runs_edges, dim3(grid_for(nl)), dim3(zc::ZC_BLOCK), 0, st, lk, lr, (zc::u32)len, (zc::u32)t, (zc::u32)nb,
+                                   buckets, present, nk, nr);
+            if (nl <= 1) break;                    // one lane saw the whole list: nothing is left open
+            if (level > 40) return fail(ZC_ERR_HIP, "MSM: segmented reduction did not converge");
+            lk = nk;
+            lr = nr;
+            len = 2 * nl;
+        }
+    }
+    // bucket reduction: one lane per segment -> sum_j (first' + j + 1) B_(first + j), the product by first' included
+    u64* cur = seg_out;
+    u64* nxt = fold_b;
+    if (nsegg <= quad_max)
+        hipLaunchKernelGGL(zc::k_msm_segments_quad, dim3((unsigned)((nsegg + 63) / 64)), dim3(zc::ZC_BLOCK), 0, st, (const zc::u32*)(buckets + b0 * zc::MSM_RAW_WORDS),
+                           (const uint8_t*)(present + b0), cur, nsegg, c, seg);
+    else
+        hipLaunchKernelGGL(zc::k_msm_segments, dim3(grid_for(nsegg)), dim3(zc::ZC_BLOCK), 0, st, (const zc::u32*)(buckets + b0 * zc::MSM_RAW_WORDS),
+                           (const uint8_t*)(present + b0), cur, nsegg, c, seg);
+    // fold every window's segment sums (a power of two per window) to one point per window:
+    // one workgroup per group of up to 128 points (four lanes per addition) or 512, two launches
+    size_t left = nsegg;
+    while (left > (size_t)nw) {
+#if ZC_MSM_FOLD_QUAD
+        const size_t fg = std::min<size_t>(128, left / (size_t)nw);
+        hipLaunchKernelGGL(zc::k_msm_fold_groups_quad, dim3((unsigned)(left / fg)), dim3(zc::ZC_BLOCK), 0, st, (const u64*)cur, nxt, (zc::u32)fg);
+#else
+        const size_t fg = std::min<size_t>(512, left / (size_t)nw);
+        hipLaunchKernelGGL(zc::k_msm_fold_groups, dim3((unsigned)(left / fg)), dim3(zc::ZC_BLOCK), 0, st, (const u64*)cur, nxt, (zc::u32)fg);
+#endif
+        left /= fg;
+        std::swap(cur, nxt);
+    }
+    *sums = cur;
+    HIP_TRY(hipGetLastError());
+    return ZC_OK;
+}
+
 // sum_i k_i P_i of one device's shard, enqueued on D.s() without any host synchronisation;
 // *result points at the 160-byte sum in D's memory (valid until the next MSM on this device).
 int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u64** result)
@@ -912,14 +1081,7 @@ int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u
             ps = D.aux;
         }
         if (affine) {
-            // points per lane of the normalisation: a CU holds twelve of its one-wave workgroups (LDS), so 2^17 lanes = 2048 waves are
-            // one round of resident waves with room left for the key sort beside them, and 8 - 16 points amortise the lane's
-            // inversion (round 6, prefetching kernel: 2^20 pairs 4 -> 8 per lane 2.30 -> 2.26 ms, 2^21 8 -> 16 3.34 -> 3.31, flat
-            // from 10 to 16; ZC_MSM_AFFINE_CHUNK overrides)
-            int ac = (int)std::min<size_t>(16, std::max<size_t>(1, cnt >> 17));
-            if (tune.msm_affine_chunk) ac = tune.msm_affine_chunk;
-            const size_t lanes = (cnt + ac - 1) / ac;            // lane g owns points g, g + stride, ...: stride = the launch's lanes
-            hipLaunchKernelGGL(zc::k_msm_prepare_affine, dim3((unsigned)((lanes + zc::MSM_PREP_BLOCK - 1) / zc::MSM_PREP_BLOCK)), dim3(zc::MSM_PREP_BLOCK), 0, ps, dP, cached, cnt, ac, rec_words);
+            msm_prepare_affine(ps, dP, cached, cnt, tune, rec_words);
         } else {
             hipLaunchKernelGGL(aligned16(dP) ? zc::k_msm_prepare : zc::k_msm_prepare_lane, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, ps, dP, cached, cnt);
         }
@@ -937,11 +1099,9 @@ int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u
             const zc::u32* last_table = sort_table + (size_t)((plan.passes - 1) & 1) * plan.table_words;
             return last_table + ((size_t)w << lastp.bits) * lastp.ncols;
         };
+        const MsmReduceBufs rb{sorted, cached, rec_words, affine, m, nb, buckets, present, {ekeys[0], ekeys[1]}, {erecs[0], erecs[1]}, c, TE};
         for (int g = 0; g < G; g++) {
             Group& gr = grp[g];
-            const size_t b0 = (size_t)gr.w0 << (c - 1);                  // the group's first bucket
-            const int seg = mp.gseg[g];
-            const size_t nsegg = seg_off[g + 1] - seg_off[g];
             // A launch that runs beside the chain of the group above it leaves that chain room: its workgroups are padded with
             // dynamic LDS so that only `wgs` of them fit a CU (three: one wave slot per SIMD, 200 VGPRs and 39 KB of LDS stay free;
             // a chain kernel that finds every slot taken waits for a bucket-sum workgroup to retire).
@@ -954,67 +1114,14 @@ int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u
                     pad = per > own ? std::min<size_t>(per - own, 65536 - own) : 0;
                 }
             }
-            hipLaunchKernelGGL(affine ? zc::k_msm_runs_affine : zc::k_msm_runs, dim3((unsigned)((gr.nl0 + zc::MSM_RUN_BLOCK - 1) / zc::MSM_RUN_BLOCK)), dim3(zc::MSM_RUN_BLOCK), pad,
-                               D.s(), sorted, (const zc::u32*)cached, (zc::u32)m, (zc::u32)gr.T, (zc::u32)nb, buckets, present, ekeys[0], erecs[0],
-                               G == 1 ? (const zc::u32*)nullptr : window_start(gr.w0), G == 1 ? (const zc::u32*)nullptr : window_start(gr.w0 + gr.nw),
-                               (zc::u32)gr.nl0, (zc::u32)gr.slot0, rec_words);
             hipStream_t st = ZC_MSM_TAIL_SIDE ? gr.st : D.s();
-            if (st != D.s()) {
-                HIP_TRY(hipEventRecord(D.ev_grp_go[g], D.s()));
-                HIP_TRY(hipStreamWaitEvent(st, D.ev_grp_go[g], 0));
-            }
-            // deeper levels of the segmented reduction: the edge list of the level above, level by level, in short runs (a bucket
-            // cut once closes at level 1: nearly every edge of a uniform batch; the levels behind it find sentinel keys only and
-            // take 5 us each.  Runs of 64 there -- 5 launches instead of 9 -- were measured: a lane then walks 64 sentinel keys
-            // one dependent load after the other, 340 us per level instead of 5).
-            {
-                const zc::u32* lk = ekeys[0] + 2 * gr.slot0;
-                const zc::u32* lr = erecs[0] + 2 * gr.slot0 * zc::MSM_RAW_WORDS;
-                size_t len = 2 * gr.nl0;
-                for (int level = 1; gr.nl0 > 1; level++) {
-                    // runs shifted by one entry, [jT+1, (j+1)T+1), run 0 one longer
-                    const size_t t = (size_t)TE;
-                    const size_t nl = len <= t + 1 ? 1 : (len - 1 + t - 1) / t;
-                    zc::u32* nk = ekeys[level & 1] + 2 * gr.slot0;
-                    zc::u32* nr = erecs[level & 1] + 2 * gr.slot0 * zc::MSM_RAW_WORDS;
-                    if (nl <= (size_t)ZC_MSM_EDGES_QUAD)       // four lanes per run: the level is a few dependent additions on a fraction of the chip
-                        hipLaunchKernelGGL(zc::k_msm_runs_edges_quad, dim3(grid_for(4 * nl)), dim3(zc::ZC_BLOCK), 0, st, lk, lr, (zc::u32)len, (zc::u32)t, (zc::u32)nb,
-                                           buckets, present, nk, nr);
-                    else
-                        hipLaunchKernelGGL(zc::k_msm_runs_edges, dim3(grid_for(nl)), dim3(zc::ZC_BLOCK), 0, st, lk, lr, (zc::u32)len, (zc::u32)t, (zc::u32)nb,
-                                           buckets, present, nk, nr);
-                    if (nl <= 1) break;                    // one lane saw the whole list: nothing is left open
-                    if (level > 40) return fail(ZC_ERR_HIP, "zc_msm: segmented reduction did not converge");
-                    lk = nk;
-                    lr = nr;
-                    len = 2 * nl;
-                }
-            }
-            // bucket reduction: one lane per segment -> sum_j (first' + j + 1) B_(first + j), the product by first' included
-            u64* cur = seg_out + 20 * seg_off[g];
-            u64* nxt = fold_b + 20 * seg_off[g];
             // few segments (the lowest group, small shards): four lanes per segment, three multiplication latencies per addition
             const size_t quad_max = (size_t)ZC_MSM_SEG_QUAD * (G > 1 && g == G - 1 ? 2 : 1);     // (the exposed chain: lanes for latency)
-            if (nsegg <= quad_max)
-                hipLaunchKernelGGL(zc::k_msm_segments_quad, dim3((unsigned)((nsegg + 63) / 64)), dim3(zc::ZC_BLOCK), 0, st, (const zc::u32*)(buckets + b0 * zc::MSM_RAW_WORDS),
-                                   (const uint8_t*)(present + b0), cur, nsegg, c, seg);
-            else
-                hipLaunchKernelGGL(zc::k_msm_segments, dim3(grid_for(nsegg)), dim3(zc::ZC_BLOCK), 0, st, (const zc::u32*)(buckets + b0 * zc::MSM_RAW_WORDS),
-                                   (const uint8_t*)(present + b0), cur, nsegg, c, seg);
-            // fold every window's segment sums (a power of two per window) to one point per window:
-            // one workgroup per group of up to 128 points (four lanes per addition) or 512, two launches
-            size_t left = nsegg;
-            while (left > (size_t)gr.nw) {
-#if ZC_MSM_FOLD_QUAD
-                const size_t fg = std::min<size_t>(128, left / (size_t)gr.nw);
-                hipLaunchKernelGGL(zc::k_msm_fold_groups_quad, dim3((unsigned)(left / fg)), dim3(zc::ZC_BLOCK), 0, st, (const u64*)cur, nxt, (zc::u32)fg);
-#else
-                const size_t fg = std::min<size_t>(512, left / (size_t)gr.nw);
-                hipLaunchKernelGGL(zc::k_msm_fold_groups, dim3((unsigned)(left / fg)), dim3(zc::ZC_BLOCK), 0, st, (const u64*)cur, nxt, (zc::u32)fg);
-#endif
-                left /= fg;
-                std::swap(cur, nxt);
-            }
+            u64* cur = nullptr;
+            if (int rc = msm_reduce_windows(D, rb, gr.w0, gr.nw, gr.T, gr.nl0, gr.slot0, G == 1 ? (const zc::u32*)nullptr : window_start(gr.w0),
+                                            G == 1 ? (const zc::u32*)nullptr : window_start(gr.w0 + gr.nw), pad, st, D.ev_grp_go[g], mp.gseg[g],
+                                            seg_off[g + 1] - seg_off[g], quad_max, seg_out + 20 * seg_off[g], fold_b + 20 * seg_off[g], &cur))
+                return rc;
             // Horner's rule, top window first across the groups: this group continues from the result of the group above it
             // (same stream, or -- the lowest group -- behind that stream's event)
             if (g == G - 1 && G > 1 && ZC_MSM_TAIL_SIDE) HIP_TRY(hipStreamWaitEvent(st, D.ev_grp_done[G - 2], 0));
@@ -1114,7 +1221,7 @@ extern "C" {
 #ifndef ZC_SRC_HASH
 #define ZC_SRC_HASH "unknown"
 #endif
-const char* zc_version(void) { return "zerocaf_hip 0.5 (gfx950, radix-2^29 Montgomery R=2^261) src:" ZC_SRC_HASH; }
+const char* zc_version(void) { return "zerocaf_hip 0.6 (gfx950, radix-2^29 Montgomery R=2^261) src:" ZC_SRC_HASH; }
 const char* zc_last_error(void) { return g_last_error.c_str(); }
 
 int zc_device_count(void)
@@ -1222,6 +1329,10 @@ int zc_ctx_destroy(zc_ctx* ctx)
         if (ds.copy_in) (void)hipStreamDestroy(ds.copy_in);
         if (ds.copy_out) (void)hipStreamDestroy(ds.copy_out);
         if (ds.stream) (void)hipStreamDestroy(ds.stream);
+    }
+    for (auto& kv : ctx->bases) {
+        (void)hipSetDevice(ctx->devs[(size_t)kv.second.slot].device);
+        (void)hipFree(kv.second.recs);
     }
     delete ctx;
     return ZC_OK;
@@ -1900,6 +2011,164 @@ int zc_msm_plan(zc_ctx* ctx, size_t n, int points_aligned16, int32_t* out, int n
     const int32_t v[17] = {p.c, p.W, p.affine ? 1 : 0, b ? (p.affine ? zc::MSM_AFF_WORDS * 4 : 128) : 0, b ? p.gT[0] : 0, p.seg, p.sort.passes, b ? p.G : 0, b ? p.rec_bytes : 0,
                            p.gw[0], p.gw[1], p.gw[2], p.gw[3], p.gT[0], p.gT[1], p.gT[2], p.gT[3]};
     memcpy(out, v, sizeof(int32_t) * (size_t)std::min(nout, 17));
+    return ZC_OK;
+}
+
+// ---- fixed-base MSM: tables of precomputed bases, batched over scalar vectors
+
+int zc_msm_bases_create(zc_ctx* ctx, const uint64_t* points, size_t n, int window_bits, uint64_t* id_out)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    REQUIRE(points); REQUIRE(id_out);
+    int c = 0, W = 0;
+    if (int rc = msm_fixed_check(n, window_bits, &c, &W, "zc_msm_bases_create")) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    Residency rp;
+    int dp = -1;
+    residency_of(points, &rp, &dp);
+    int slot = 0;
+    if (rp == RES_DEVICE) {
+        DevState* ds = dev_state_of(ctx, dp);
+        if (!ds) return fail(ZC_ERR_MIXED_MEM, "zc_msm_bases_create: points on a device outside this context");
+        slot = (int)(ds - ctx->devs.data());
+    }
+    DevState& D = ctx->devs[(size_t)slot];
+    if (int rc = ring_check(D)) return rc;
+    HIP_TRY(hipSetDevice(D.device));
+    MsmBases t;
+    t.slot = slot;
+    t.n = n;
+    t.c = c;
+    t.W = W;
+    t.bytes = n * (size_t)W * ZC_MSM_REC_STRIDE;
+    // window 0 = the points (copied: 16-byte aligned, plain), window j = 2^c times window j - 1, each normalised into its part of
+    // the table; the two n-point buffers live for this call only
+    void* pts[2] = {nullptr, nullptr};
+    auto cleanup = [&](int rc) {
+        (void)hipStreamSynchronize(D.s());
+        for (void* b : pts)
+            if (b) (void)hipFree(b);
+        if (rc && t.recs) (void)hipFree(t.recs);
+        return rc;
+    };
+    hipError_t e = hipMalloc(&t.recs, t.bytes);
+    if (e != hipSuccess) return t.recs = nullptr, cleanup(fail(ZC_ERR_NOMEM, "zc_msm_bases_create: hipMalloc(table)", e));
+    for (int b = 0; b < 2; b++) {
+        e = hipMalloc(&pts[b], n * 160);
+        if (e != hipSuccess) return pts[b] = nullptr, cleanup(fail(ZC_ERR_NOMEM, "zc_msm_bases_create: hipMalloc(points)", e));
+    }
+    e = hipMemcpyAsync(pts[0], points, n * 160, rp == RES_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, D.s());
+    if (e != hipSuccess) return cleanup(fail(ZC_ERR_HIP, "zc_msm_bases_create: copy of the points", e));
+    const zc::u32 rec_words = ZC_MSM_REC_STRIDE / 4;
+    for (int j = 0; j < W; j++) {
+        if (j) hipLaunchKernelGGL(zc::k_msm_fixed_double, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)pts[(j - 1) & 1], (u64*)pts[j & 1], n, c);
+        msm_prepare_affine(D.s(), (const u64*)pts[j & 1], (zc::u32*)t.recs + (size_t)j * n * rec_words, n, D.tune, rec_words);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(D.s());
+    if (e != hipSuccess) return cleanup(fail(ZC_ERR_HIP, "zc_msm_bases_create: table build", e));
+    cleanup(ZC_OK);
+    const uint64_t id = g_next_bases_id.fetch_add(1);
+    ctx->bases[id] = t;
+    *id_out = id;
+    return ZC_OK;
+}
+
+int zc_msm_bases_destroy(zc_ctx* ctx, uint64_t id)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    auto it = ctx->bases.find(id);
+    if (it == ctx->bases.end()) return fail(ZC_ERR_BAD_ARG, "zc_msm_bases_destroy: no live table of this context has this id");
+    DevState& D = ctx->devs[(size_t)it->second.slot];
+    HIP_TRY(hipSetDevice(D.device));
+    HIP_TRY(hipStreamSynchronize(D.s()));
+    void* recs = it->second.recs;
+    ctx->bases.erase(it);
+    HIP_TRY(hipFree(recs));
+    return ZC_OK;
+}
+
+// out_points[b] = sum_i k[b][i] P_i: digits of every vector (one launch), ONE key sort over the batch's vectors as its windows,
+// then the lower half of the bucket method (msm_reduce_windows) down to one sum per vector, copied to the host.
+int zc_msm_fixed(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, size_t batch, uint64_t* out_points)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    auto it = ctx->bases.find(id);
+    if (it == ctx->bases.end()) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: no live table of this context has this id");
+    if (batch == 0) return ZC_OK;
+    REQUIRE(scalars); REQUIRE(out_points);
+    const MsmBases& t = it->second;
+    const size_t n = t.n;
+    const int c = t.c;
+    if (batch >= ((size_t)1 << 32) / (n * (size_t)t.W) + 1 || batch * n * (size_t)t.W >= ((size_t)1 << 32))
+        return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x n x W does not fit 32-bit pair indices");
+    if (batch >= ((size_t)1 << (33 - c)))
+        return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x 2^(c-1) buckets do not fit 32-bit bucket keys");
+    DevState& D = ctx->devs[(size_t)t.slot];
+    Residency rk;
+    int dk = -1;
+    residency_of(scalars, &rk, &dk);
+    if (rk == RES_DEVICE && dk != D.device) return fail(ZC_ERR_MIXED_MEM, "zc_msm_fixed: scalars on another device than the table");
+    if (int rc = ring_check(D)) return rc;
+    HIP_TRY(hipSetDevice(D.device));
+    const u64* dK = scalars;
+    if (rk == RES_HOST) {
+        if (int rc = ensure(&D.scratch[1], &D.scratch_bytes[1], batch * n * 40)) return rc;
+        HIP_TRY(hipMemcpyAsync(D.scratch[1], scalars, batch * n * 40, hipMemcpyHostToDevice, D.s()));
+        dK = (const u64*)D.scratch[1];
+    }
+    const MsmFixedPlan fp = msm_fixed_plan(n, c, batch, D.tune);
+    const MsmSortPlan& plan = fp.sort;
+    const size_t m = fp.m, nb = fp.nb;
+    for (int pass = 0; pass < 2; pass++) {
+        Carver cv{pass ? (char*)D.msm : nullptr};
+        zc::u32* digits = cv.take<zc::u32>(m);
+        uint2* pairs_a = cv.take<uint2>(m);
+        void* pairs_b = plan.passes == 1 ? nullptr : plan.packed ? (void*)cv.take<zc::u32>(m) : (void*)cv.take<uint2>(m);
+        zc::u32* sort_table = cv.take<zc::u32>(2 * plan.table_words);
+        zc::u32* sort_sums = cv.take<zc::u32>(plan.table_words / zc::SCAN_BLOCK_ELEMS + 1);
+        zc::u32* buckets = cv.take<zc::u32>(nb * zc::MSM_RAW_WORDS);
+        uint8_t* present = cv.take<uint8_t>(nb);
+        zc::u32* ekeys[2] = {cv.take<zc::u32>(2 * fp.nl0), cv.take<zc::u32>(2 * fp.nl0)};
+        zc::u32* erecs[2] = {cv.take<zc::u32>(2 * fp.nl0 * zc::MSM_RAW_WORDS), cv.take<zc::u32>(2 * fp.nl0 * zc::MSM_RAW_WORDS)};
+        u64* seg_out = cv.take<u64>(fp.nseg * 20);
+        u64* fold_b = cv.take<u64>(fp.nseg * 20);
+        if (!pass) {
+            if (int rc = ensure(&D.msm, &D.msm_bytes, cv.off)) return rc;
+            continue;
+        }
+        hipLaunchKernelGGL(zc::k_msm_fixed_digits, dim3(grid_for(batch * n)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, digits, n, batch, c, t.W);
+        HIP_TRY(hipMemsetAsync(present, 0, nb, D.s()));
+        if (int rc = msm_sort(D, D.s(), plan, 0, (int)batch, digits, pairs_a, pairs_b, sort_table, plan.table_words, sort_sums)) return rc;
+        const MsmReduceBufs rb{pairs_a, (const zc::u32*)t.recs, (zc::u32)(ZC_MSM_REC_STRIDE / 4), true, m, nb, buckets, present,
+                               {ekeys[0], ekeys[1]}, {erecs[0], erecs[1]}, c, fp.TE};
+        u64* sums = nullptr;
+        if (int rc = msm_reduce_windows(D, rb, 0, (int)batch, fp.T, fp.nl0, 0, nullptr, nullptr, 0, D.s(), nullptr, fp.seg, fp.nseg,
+                                        (size_t)ZC_MSM_SEG_QUAD, seg_out, fold_b, &sums))
+            return rc;
+        // the folds leave the batch's sums as canonical extended points, one per vector in order
+        HIP_TRY(hipMemcpyAsync(out_points, sums, batch * 160, hipMemcpyDeviceToHost, D.s()));
+        HIP_TRY(hipStreamSynchronize(D.s()));
+    }
+    return ZC_OK;
+}
+
+// What a table of n bases would be (window_bits 0 = the library's choice) -- a query, no device work.  Writes min(nout, 8)
+// entries (nout >= 8): [0] window bits c, [1] windows W, [2] record stride in bytes, [3] run length of the bucket-sum kernel
+// and [4] buckets per reduction segment for one scalar vector, [5] sort passes, [6] table MiB (rounded up), [7] window groups (1).
+int zc_msm_fixed_plan(zc_ctx* ctx, size_t n, int window_bits, int32_t* out, int nout)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    REQUIRE(out);
+    if (nout < 8) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed_plan: nout < 8");
+    int c = 0, W = 0;
+    if (int rc = msm_fixed_check(n, window_bits, &c, &W, "zc_msm_fixed_plan")) return rc;
+    const MsmFixedPlan p = msm_fixed_plan(n, c, 1, ctx->devs[0].tune);
+    const size_t mib = (n * (size_t)W * ZC_MSM_REC_STRIDE + ((size_t)1 << 20) - 1) >> 20;
+    const int32_t v[8] = {c, W, ZC_MSM_REC_STRIDE, p.T, p.seg, p.sort.passes, (int32_t)mib, 1};
+    memcpy(out, v, sizeof v);
     return ZC_OK;
 }
 

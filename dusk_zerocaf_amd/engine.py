@@ -452,6 +452,18 @@ class Engine:
         self._call("zc_msm", pp, pk, n, out.ctypes.data)
         return out
 
+    def msm_bases(self, points, window_bits=0):
+        """A fixed-base table of the (n, 20) points (zc_msm_bases_create): `MsmBases.msm(scalars)` then runs the MSM of one
+        or many scalar vectors against them without re-normalising the points.  window_bits 0 = the library's choice."""
+        return MsmBases(self, points, window_bits)
+
+    def msm_fixed_plan(self, n, window_bits=0):
+        """What a table of n bases would be (a query, no device work)."""
+        v = (C.c_int32 * 8)()
+        self._call("zc_msm_fixed_plan", int(n), int(window_bits), v, 8)
+        return {"window_bits": v[0], "windows": v[1], "record_stride": v[2], "run": v[3], "segment_buckets": v[4],
+                "sort_passes": v[5], "table_mib": v[6], "window_groups": v[7]}
+
     # ---- the exchange step of a sharded MSM (BASELINE configs[4])
     def msm_partial(self, points, scalars, out=None):
         """This device's sum left in device memory: a (1, 20) int64 torch CUDA tensor (asynchronous)."""
@@ -513,3 +525,53 @@ class Engine:
     @staticmethod
     def host_unregister(arr: np.ndarray):
         _lib.check(_lib.load().zc_host_unregister(arr.ctypes.data), "zc_host_unregister")
+
+
+class MsmBases:
+    """A fixed-base MSM table owned by an Engine's context (Engine.msm_bases).  `.msm(scalars)`: (n, 5) scalars give a (1, 20)
+    numpy array, (batch, n, 5) give (batch, 20); numpy or device-resident torch scalars.  `.plan`: what the table was built
+    with (zc_msm_fixed_plan).  `.close()` frees the table; also usable as a context manager."""
+
+    def __init__(self, engine, points, window_bits=0):
+        self.engine = engine
+        self.id = 0
+        points, pp, n = engine._prep(points, 20, np.uint64)
+        self.n = n
+        self.plan = engine.msm_fixed_plan(n, window_bits)
+        out = C.c_uint64(0)
+        engine._call("zc_msm_bases_create", pp, n, int(window_bits), C.byref(out))
+        self.id = out.value
+
+    def msm(self, scalars):
+        if self.id == 0:
+            raise _lib.ZerocafHipError("MsmBases: the table was closed")
+        shape = tuple(scalars.shape)
+        assert len(shape) in (2, 3) and shape[-2:] == (self.n, 5), (shape, self.n)
+        batch = 1 if len(shape) == 2 else shape[0]
+        if _is_torch(scalars):
+            assert scalars.is_contiguous() and scalars.element_size() == 8
+            self.engine._follow_torch_stream(scalars)
+            pk = scalars.data_ptr()
+        else:
+            scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+            pk = scalars.ctypes.data
+        out = np.empty((batch, 20), dtype=np.uint64)
+        self.engine._call("zc_msm_fixed", C.c_uint64(self.id), pk, batch, out.ctypes.data)
+        return out
+
+    def close(self):
+        if self.id and self.engine.ctx:
+            self.engine._call("zc_msm_bases_destroy", C.c_uint64(self.id))
+        self.id = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

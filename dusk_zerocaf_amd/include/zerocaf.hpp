@@ -639,6 +639,62 @@ inline std::array<int32_t, 17> msm_plan(size_t n, bool points_aligned16 = true)
     Backend::check(zc_msm_plan(Backend::ctx(), n, points_aligned16 ? 1 : 0, v.data(), 17), "zc_msm_plan");
     return v;
 }
+// A fixed-base MSM table (zc_msm_bases_create), freed when the object goes: msm() of one or many scalar vectors against the
+// same bases, each result equal to msm(bases, ks) under ==
+class MsmBases {
+public:
+    explicit MsmBases(const std::vector<EdwardsPoint>& ps, int window_bits = 0) : n_(ps.size())
+    {
+        std::vector<uint64_t> p(ps.size() * 20);
+        for (size_t i = 0; i < ps.size(); i++) ps[i].flat(&p[20 * i]);
+        Backend::check(zc_msm_bases_create(Backend::ctx(), p.data(), ps.size(), window_bits, &id_), "zc_msm_bases_create");
+    }
+    MsmBases(const MsmBases&) = delete;
+    MsmBases& operator=(const MsmBases&) = delete;
+    MsmBases(MsmBases&& o) noexcept : id_(o.id_), n_(o.n_) { o.id_ = 0; }
+    MsmBases& operator=(MsmBases&& o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            id_ = o.id_;
+            n_ = o.n_;
+            o.id_ = 0;
+        }
+        return *this;
+    }
+    ~MsmBases() { reset(); }
+    size_t size() const { return n_; }
+    // kss: batch vectors of size() scalars each -> batch sums
+    std::vector<EdwardsPoint> msm(const std::vector<std::vector<Scalar>>& kss) const
+    {
+        std::vector<uint64_t> k(kss.size() * n_ * 5), o(kss.size() * 20);
+        for (size_t b = 0; b < kss.size(); b++) {
+            if (kss[b].size() != n_) throw std::invalid_argument("MsmBases::msm: a scalar vector of the wrong length");
+            for (size_t i = 0; i < n_; i++) std::memcpy(&k[5 * (b * n_ + i)], kss[b][i].l.data(), 40);
+        }
+        Backend::check(zc_msm_fixed(Backend::ctx(), id_, k.data(), kss.size(), o.data()), "zc_msm_fixed");
+        std::vector<EdwardsPoint> out(kss.size());
+        for (size_t b = 0; b < kss.size(); b++) out[b] = EdwardsPoint::unflat(&o[20 * b]);
+        return out;
+    }
+    EdwardsPoint msm(const std::vector<Scalar>& ks) const { return msm(std::vector<std::vector<Scalar>>{ks})[0]; }
+    // {c, W, record stride bytes, run length, segment buckets, sort passes, table MiB, window groups} of a table of n bases
+    static std::array<int32_t, 8> plan(size_t n, int window_bits = 0)
+    {
+        std::array<int32_t, 8> v{};
+        Backend::check(zc_msm_fixed_plan(Backend::ctx(), n, window_bits, v.data(), 8), "zc_msm_fixed_plan");
+        return v;
+    }
+
+private:
+    void reset()
+    {
+        if (id_) zc_msm_bases_destroy(Backend::ctx(), id_);
+        id_ = 0;
+    }
+    uint64_t id_ = 0;
+    size_t n_ = 0;
+};
 // key generation: (RISTRETTO_BASEPOINT * k).compress(), identical bytes
 inline std::vector<CompressedRistretto> ristretto_keygen_batch(const std::vector<Scalar>& ks)
 {

@@ -273,6 +273,26 @@ int zc_comm_size(zc_ctx *ctx, int *ranks);
 int zc_msm_sharded(zc_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t n_local,
                    uint64_t *out_point);
 
+/* ---- fixed-base MSM (ABI 0.6): precomputed bases, batched over scalar vectors ---------------------------------------- */
+/* For callers whose bases do not change between calls (commitment keys: Pedersen vector commitments, Bulletproofs
+ * generators, an SRS).  A table is owned by the context and named by an id; a destroyed or foreign id is ZC_ERR_BAD_ARG.
+ *   zc_msm_bases_create   precompute the table of n >= 1 bases: record j*n+i = affine record of 2^(c j) P_i, j < W = ceil(261 / c),
+ *                         on the device that owns `points` (host points: device slot 0).  window_bits 0 = the library's choice,
+ *                         else 5..22; n*W >= 2^31 -> ZC_ERR_BAD_ARG (checked before anything is allocated).  *id_out: nonzero,
+ *                         never reused in the process.  A one-time cost of about 261 doublings per base.
+ *   zc_msm_bases_destroy  frees the table (zc_ctx_destroy frees every live one)
+ *   zc_msm_fixed          out_points[b] = sum_i k[b][i] * P_i for b < batch (scalars: batch x n x 5 limbs, batch-major, HOST memory
+ *                         or the table's device -- another device: ZC_ERR_MIXED_MEM), each equal under == to the reference's sum
+ *                         of `&P_i * &k_i`, like zc_msm.  out_points: HOST, batch x 20.  batch == 0: ZC_OK, nothing written;
+ *                         batch*n*W >= 2^32 -> ZC_ERR_BAD_ARG.  Synchronous; zc_msm and zc_msm_fixed calls interleave freely.
+ *   zc_msm_fixed_plan     a query, no device work: writes min(nout, 8) entries (nout >= 8) for a table of n bases and
+ *                         window_bits (0 = auto): {c, W, record stride bytes, run length and segment buckets of one vector's
+ *                         call, sort passes, table MiB, window groups}; fails with ZC_ERR_BAD_ARG where create would.          */
+int zc_msm_bases_create(zc_ctx *ctx, const uint64_t *points, size_t n, int window_bits, uint64_t *id_out);
+int zc_msm_bases_destroy(zc_ctx *ctx, uint64_t id);
+int zc_msm_fixed(zc_ctx *ctx, uint64_t id, const uint64_t *scalars, size_t batch, uint64_t *out_points);
+int zc_msm_fixed_plan(zc_ctx *ctx, size_t n, int window_bits, int32_t *out, int nout);
+
 #ifdef __cplusplus
 }
 #endif

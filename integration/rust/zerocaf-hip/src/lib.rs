@@ -213,6 +213,39 @@ impl Drop for HipBackend {
     }
 }
 
+/// A fixed-base MSM table owned by a backend's context (`HipBackend::msm_bases`); destroyed on drop.
+pub struct MsmBases<'a> {
+    backend: &'a HipBackend,
+    id: u64,
+    n: usize,
+}
+
+impl Drop for MsmBases<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            ffi::zc_msm_bases_destroy(self.backend.ctx, self.id);
+        }
+    }
+}
+
+impl MsmBases<'_> {
+    pub fn len(&self) -> usize {
+        self.n
+    }
+
+    /// One sum per scalar vector (each of `len()` scalars), equal to `HipBackend::msm` of the same pairs under `==`.
+    pub fn msm(&self, kss: &[Vec<Scalar>]) -> Result<Vec<EdwardsPoint>> {
+        let mut fk = Vec::with_capacity(kss.len() * self.n * 5);
+        for ks in kss {
+            assert_eq!(ks.len(), self.n);
+            fk.extend(flat_sc(ks));
+        }
+        let mut out = vec![0u64; 20 * kss.len()];
+        check(unsafe { ffi::zc_msm_fixed(self.backend.ctx, self.id, fk.as_ptr(), kss.len(), out.as_mut_ptr()) })?;
+        Ok(unflat_ed(&out))
+    }
+}
+
 impl HipBackend {
     /// `devices = &[]` uses the current HIP device; more than one device shards host batches
     /// into contiguous ranges (independent elements, no exchange step).
@@ -604,6 +637,23 @@ impl HipBackend {
         let mut out = vec![0u64; 20];
         check(unsafe { ffi::zc_msm(self.ctx, fp.as_ptr(), fk.as_ptr(), p.len(), out.as_mut_ptr()) })?;
         Ok(unflat_ed(&out)[0])
+    }
+
+    /// A fixed-base table of `p` (`zc_msm_bases_create`): later MSMs against the same bases skip their normalisation,
+    /// doublings and Horner's rule, and many scalar vectors go through one call.  `window_bits = 0`: the library's choice.
+    pub fn msm_bases(&self, p: &[EdwardsPoint], window_bits: i32) -> Result<MsmBases<'_>> {
+        let fp = flat_ed(p);
+        let mut id = 0u64;
+        check(unsafe { ffi::zc_msm_bases_create(self.ctx, fp.as_ptr(), p.len(), window_bits, &mut id) })?;
+        Ok(MsmBases { backend: self, id, n: p.len() })
+    }
+
+    /// What a table of `n` bases would be (a query, no device work): `[c, W, record stride bytes, run length, buckets per
+    /// segment, sort passes, table MiB, window groups]`.
+    pub fn msm_fixed_plan(&self, n: usize, window_bits: i32) -> Result<[i32; 8]> {
+        let mut v = [0i32; 8];
+        check(unsafe { ffi::zc_msm_fixed_plan(self.ctx, n, window_bits, v.as_mut_ptr(), 8) })?;
+        Ok(v)
     }
 
     // -------------------------------------------------------------- sharded MSM: the exchange step

@@ -850,4 +850,55 @@ ZC_KERNEL void k_msm_fixed_digits(const u64* k, u32* keys, size_t n, size_t batc
     msm_digit_keys(k + 5 * g, keys + b * n * (size_t)W + i, n, c, W);
 }
 
+// ---------------------------------------------------------------- batched variable bases (zc_msm_batch)
+// `batch` independent MSMs of n pairs each, instance-major (pair b n + i).  Bucket regime: k_msm_fixed_digits writes every
+// instance's digits in one launch, and its layout is already the one wanted here -- sort window w' = b W + j holds instance
+// b's window j, n keys at keys[(b W + j) n + i].  The sort names the in-window index i; the record of pair (b, i) is b n + i.
+// One lane per sorted pair adds b n, b = bucket key / (W 2^(c-1)).  The zero-digit tail (key 0xFFFFFFFF, behind every bucket)
+// keeps its index i < n: k_msm_runs never adds it, but may prefetch its record, and i is a record in bounds.
+ZC_KERNEL void k_msm_batch_rebase(uint2* pairs, size_t m, u32 nbuckets, u32 inst_buckets, u32 n)
+{
+    const size_t e = gid();
+    if (e >= m) return;
+    const uint2 p = pairs[e];
+    if (p.x >= nbuckets) return;
+    pairs[e].y = p.y + (p.x / inst_buckets) * n;                // b n + i < 2^31: the sign bit stays where it is
+}
+// Horner's rule of k_msm_window_combine for every instance at once: one quad of lanes per instance, 16 per 64-lane workgroup.
+// windows[b W + j] = S_(b, j); out[b] = sum_j 2^(c j) S_(b, j).  Literal-identity windows above an instance's longest scalar
+// need no doublings.  The chain of about c (W - 1) doublings is paid once per call, not once per instance.
+ZC_KERNEL void k_msm_window_combine_batch(const u64* windows, u64* out, size_t batch, int W, int c)
+{
+    const int role = threadIdx.x & 3;
+    const size_t b = (size_t)blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2);
+    if (b >= batch) return;                                       // whole quads leave together
+    const u64* sb = windows + 20 * (size_t)W * b;
+    pt Q = pt_identity();
+    bool started = false;
+    for (int w = W - 1; w >= 0; w--) {
+        const u64* sw = sb + 20 * (size_t)w;
+        if (started)
+            for (int i = 0; i < c; i++) Q = pt_double_quad(Q, role);
+        if (!msm_is_literal_identity(sw)) {
+            const pt S = pt_load(sw);
+            Q = started ? pt_add<true>(Q, S) : S;
+            started = true;
+        }
+    }
+    if (role == 0) pt_store(out + 20 * b, Q);
+}
+// Small-instance regime: one level of the pairwise fold of k_ed_fold_pairs, segmented by instance.  Row b of `in` holds n_in
+// consecutive points; row b of `out` gets (n_in + 1) / 2: point i = in[2 i] + in[2 i + 1], the odd one out copied.  Rows never mix.
+ZC_KERNEL void k_msm_fold_rows(const u64* in, u64* out, size_t batch, size_t n_in)
+{
+    const size_t n_out = (n_in + 1) / 2;
+    const size_t g = gid();
+    if (g >= batch * n_out) return;
+    const size_t b = g / n_out, i = g - b * n_out;
+    const u64* row = in + 20 * n_in * b;
+    const pt a = pt_load(row + 20 * (2 * i));
+    if (2 * i + 1 < n_in) pt_store(out + 20 * g, pt_add(a, pt_load(row + 20 * (2 * i + 1))));
+    else pt_store(out + 20 * g, a);
+}
+
 }  // namespace zc

@@ -555,27 +555,29 @@ int ring_check(DevState& D)
     return fail(ZC_ERR_HIP, "windowed core: a wave timed out waiting for its table slot; the rows it owned hold poison (all ones) -- "
                             "the outputs of the last windowed-core calls on this device are not valid");
 }
+// cnt strict scalar multiplications of device arrays on D.s(): the kernel choice of zc_ed_scalar_mul
+void scalar_mul_on_device(DevState& D, const u64* p, const u64* k, u64* out, size_t cnt)
+{
+    if (cnt >= PW_MIN_ELEMS && !D.tune.sched_block) {
+        zc::u32* counter = nullptr;
+        if (const zc::u32* perm = balance_index(D, k, cnt, &counter)) {
+            hipLaunchKernelGGL(zc::k_ed_scalar_mul_pw, dim3((unsigned)(3 * D.cus)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, perm, counter, (zc::u32)cnt);
+            return;
+        }
+    }
+    if (cnt <= QUAD_LAUNCH_ELEMS) {
+        // four lanes per element: the batch cannot fill the chip anyway, so buy latency with lanes
+        hipLaunchKernelGGL(zc::k_ed_scalar_mul_quad, dim3((unsigned)((cnt + 63) / 64)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, cnt);
+        return;
+    }
+    hipLaunchKernelGGL(strict_kernel_for(cnt), dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, (size_t)5, out, cnt);
+}
 int scalar_mul_impl(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t* out, size_t n)
 {
     REQUIRE(p); REQUIRE(k); REQUIRE(out);
     Arg args[3] = {in_arg(p, 160), in_arg(k, 40), out_arg(out, 160)};
     return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        if (cnt >= PW_MIN_ELEMS && !D.tune.sched_block) {
-            zc::u32* counter = nullptr;
-            if (const zc::u32* perm = balance_index(D, (const u64*)d[1], cnt, &counter)) {
-                hipLaunchKernelGGL(zc::k_ed_scalar_mul_pw, dim3((unsigned)(3 * D.cus)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1],
-                                   (u64*)d[2], perm, counter, (zc::u32)cnt);
-                return;
-            }
-        }
-        if (cnt <= QUAD_LAUNCH_ELEMS) {
-            // four lanes per element: the batch cannot fill the chip anyway, so buy latency with lanes
-            hipLaunchKernelGGL(zc::k_ed_scalar_mul_quad, dim3((unsigned)((cnt + 63) / 64)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0],
-                               (const u64*)d[1], (u64*)d[2], cnt);
-            return;
-        }
-        hipLaunchKernelGGL(strict_kernel_for(cnt), dim3(grid_for(cnt)),
-                           dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (size_t)5, (u64*)d[2], cnt);
+        scalar_mul_on_device(D, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], cnt);
     }, true);
 }
 // the same scalar for every point, handed to the kernel by value
@@ -1207,6 +1209,151 @@ int msm_shard(DevState& ds, const uint64_t* points, const uint64_t* scalars, siz
         dK = (const u64*)ds.scratch[1];
     }
     return msm_on_device(ds, dP, dK, cnt, result);
+}
+
+// ---------------------------------------------------------------- batched variable-base MSM (zc_msm_batch)
+// `batch` independent MSMs of n pairs each, instance-major.  Instances of at least this many pairs take the bucket regime
+// (every instance's windows are sort windows of one key sort; one bucket reduction and one parallel Horner step for all);
+// below it, batch n strict scalar multiplications and a pairwise fold per instance.  Sweep at 2^20 pairs in all
+// (tools/bench_msm_batch.py --sweep, profiles/r08_msm_batch_sweep.json): see DESIGN.md section 7.2.
+#ifndef ZC_MSM_BATCH_BUCKET_MIN_N
+#define ZC_MSM_BATCH_BUCKET_MIN_N 64
+#endif
+constexpr size_t MSM_BATCH_BUCKET_MIN_N = ZC_MSM_BATCH_BUCKET_MIN_N;
+// Window width of the bucket regime, per instance: the bucket sums cost n W additions and the reduction about 3.7 per bucket,
+// 2^(c-1) buckets per window: c minimises ceil(261 / c) (n + 3.7 2^(c-1)) (about 9 at n = 2^12).  The Horner step's chain is
+// shared by all instances, so it does not enter the per-instance cost.  ZC_MSM_WINDOW=c overrides, as for zc_msm.
+int msm_batch_window_bits(size_t n, const Tuning& tune)
+{
+    if (tune.msm_window >= zc::MSM_MIN_C && tune.msm_window <= zc::MSM_MAX_C) return tune.msm_window;
+    int best = zc::MSM_MIN_C;
+    double best_cost = 0;
+    for (int c = zc::MSM_MIN_C; c <= zc::MSM_MAX_C; c++) {
+        const double cost = (double)((zc::MSM_SCALAR_BITS + c - 1) / c) * ((double)n + 3.7 * (double)((size_t)1 << (c - 1)));
+        if (c == zc::MSM_MIN_C || cost < best_cost) best = c, best_cost = cost;
+    }
+    return best;
+}
+struct MsmBatchPlan {
+    bool buckets = false;          // false: batch n scalar multiplications + a pairwise fold per instance
+    int c = 0, W = 0;              // window bits and windows of the bucket regime (the limits are checked with them in both regimes)
+    bool affine = false;           // affine records (batch n >= 2^17 and 16-byte aligned points), else projective
+    int T = 0, TE = 8, seg = 0;    // run lengths (level 0, deeper levels), buckets per reduction segment
+    size_t m = 0, nb = 0, nseg = 0, nl0 = 0;   // list entries (batch n W), buckets (batch W 2^(c-1)), segments, level-0 lanes
+    int rec_bytes = 128;           // stride of the cached records
+    MsmSortPlan sort;
+};
+MsmBatchPlan msm_batch_plan(size_t n, size_t batch, bool points_aligned16, const Tuning& tune)
+{
+    MsmBatchPlan p;
+    if (n == 0 || batch == 0) return p;
+    p.c = msm_batch_window_bits(n, tune);
+    p.W = (zc::MSM_SCALAR_BITS + p.c - 1) / p.c;
+    if (n < MSM_BATCH_BUCKET_MIN_N) return p;
+    p.buckets = true;
+    const size_t nw = batch * (size_t)p.W;                    // sort windows
+    p.m = nw * n;
+    p.nb = nw << (p.c - 1);
+    p.sort = msm_sort_plan(n, p.c, (int)nw, tune);
+    p.affine = msm_affine(batch * n, tune) && points_aligned16;
+    p.rec_bytes = p.affine ? ZC_MSM_REC_STRIDE : 128;
+    p.T = msm_run_length(p.m, tune);
+    if (tune.msm_run_edges) p.TE = tune.msm_run_edges & ~1;
+    p.seg = tune.msm_seg ? tune.msm_seg : zc::msm_segment_buckets(p.nb);
+    while (p.seg > (1 << (p.c - 1))) p.seg >>= 1;          // a segment never spans windows
+    p.nseg = p.nb / (size_t)p.seg;
+    p.nl0 = (p.m + (size_t)p.T - 1) / (size_t)p.T;
+    return p;
+}
+// The index limits of a batch, checked before anything is allocated: record indices batch n < 2^31, pair indices
+// batch n W < 2^32, bucket keys batch W 2^(c-1) < 2^32 (c, W: the bucket regime's, whichever regime runs).
+int msm_batch_check(size_t n, size_t batch, const Tuning& tune, const char* who)
+{
+    if (n == 0 || batch == 0) return ZC_OK;
+    char msg[160];
+    const size_t lim31 = (size_t)1 << 31, lim32 = (size_t)1 << 32;
+    if (n >= lim31 || batch >= lim31 || n * batch >= lim31)
+        return snprintf(msg, sizeof msg, "%s: %zu instances x %zu pairs do not fit 31-bit record indices", who, batch, n), fail(ZC_ERR_BAD_ARG, msg);
+    const int c = msm_batch_window_bits(n, tune);
+    const size_t W = (size_t)((zc::MSM_SCALAR_BITS + c - 1) / c);
+    if (n * batch * W >= lim32)
+        return snprintf(msg, sizeof msg, "%s: %zu instances x %zu pairs x %zu windows do not fit 32-bit pair indices", who, batch, n, W), fail(ZC_ERR_BAD_ARG, msg);
+    if ((batch * W) << (c - 1) >= lim32)
+        return snprintf(msg, sizeof msg, "%s: %zu instances x %zu windows x 2^%d buckets do not fit 32-bit bucket keys", who, batch, W, c - 1), fail(ZC_ERR_BAD_ARG, msg);
+    return ZC_OK;
+}
+// The batch's sums, enqueued on D.s() without any host synchronisation: *result = batch canonical points in D.msm (valid until
+// the next MSM on this device).  batch >= 2, n >= 1, limits checked.
+int msm_batch_on_device(DevState& D, const u64* dP, const u64* dK, size_t n, size_t batch, const u64** result)
+{
+    const Tuning& tune = D.tune;
+    const MsmBatchPlan bp = msm_batch_plan(n, batch, aligned16(dP), tune);
+    const size_t cnt = n * batch;
+    if (!bp.buckets) {
+        for (int pass = 0; pass < 2; pass++) {
+            Carver cv{pass ? (char*)D.msm : nullptr};
+            u64* prod = cv.take<u64>(cnt * 20);
+            u64* half = cv.take<u64>(batch * ((n + 1) / 2) * 20);
+            if (!pass) {
+                if (int rc = ensure(&D.msm, &D.msm_bytes, cv.off)) return rc;
+                continue;
+            }
+            scalar_mul_on_device(D, dP, dK, prod, cnt);
+            // every level halves every row: rows of n, ceil(n / 2), ... points, ping-pong between the two buffers
+            u64* cur = prod;
+            u64* nxt = half;
+            for (size_t len = n; len > 1; len = (len + 1) / 2) {
+                hipLaunchKernelGGL(zc::k_msm_fold_rows, dim3(grid_for(batch * ((len + 1) / 2))), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)cur, nxt, batch, len);
+                std::swap(cur, nxt);
+            }
+            *result = cur;
+        }
+        HIP_TRY(hipGetLastError());
+        return ZC_OK;
+    }
+    const int c = bp.c, W = bp.W;
+    const size_t m = bp.m, nb = bp.nb, nw = batch * (size_t)W;
+    const MsmSortPlan& plan = bp.sort;
+    const zc::u32 rec_words = (zc::u32)(bp.rec_bytes / 4);
+    for (int pass = 0; pass < 2; pass++) {
+        Carver cv{pass ? (char*)D.msm : nullptr};
+        zc::u32* digits = cv.take<zc::u32>(m);
+        uint2* pairs_a = cv.take<uint2>(m);
+        void* pairs_b = plan.passes == 1 ? nullptr : plan.packed ? (void*)cv.take<zc::u32>(m) : (void*)cv.take<uint2>(m);
+        zc::u32* sort_table = cv.take<zc::u32>(2 * plan.table_words);
+        zc::u32* sort_sums = cv.take<zc::u32>(plan.table_words / zc::SCAN_BLOCK_ELEMS + 1);
+        zc::u32* cached = cv.take<zc::u32>(cnt * 32);
+        zc::u32* buckets = cv.take<zc::u32>(nb * zc::MSM_RAW_WORDS);
+        uint8_t* present = cv.take<uint8_t>(nb);
+        zc::u32* ekeys[2] = {cv.take<zc::u32>(2 * bp.nl0), cv.take<zc::u32>(2 * bp.nl0)};
+        zc::u32* erecs[2] = {cv.take<zc::u32>(2 * bp.nl0 * zc::MSM_RAW_WORDS), cv.take<zc::u32>(2 * bp.nl0 * zc::MSM_RAW_WORDS)};
+        u64* seg_out = cv.take<u64>(bp.nseg * 20);
+        u64* fold_b = cv.take<u64>(bp.nseg * 20);
+        u64* out = cv.take<u64>(batch * 20);
+        if (!pass) {
+            if (int rc = ensure(&D.msm, &D.msm_bytes, cv.off)) return rc;
+            continue;
+        }
+        // one normalisation over all batch n points: it is per point, instance boundaries do not matter
+        if (bp.affine)
+            msm_prepare_affine(D.s(), dP, cached, cnt, tune, rec_words);
+        else
+            hipLaunchKernelGGL(aligned16(dP) ? zc::k_msm_prepare : zc::k_msm_prepare_lane, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dP, cached, cnt);
+        hipLaunchKernelGGL(zc::k_msm_fixed_digits, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, digits, n, batch, c, W);
+        HIP_TRY(hipMemsetAsync(present, 0, nb, D.s()));
+        if (int rc = msm_sort(D, D.s(), plan, 0, (int)nw, digits, pairs_a, pairs_b, sort_table, plan.table_words, sort_sums)) return rc;
+        hipLaunchKernelGGL(zc::k_msm_batch_rebase, dim3(grid_for(m)), dim3(zc::ZC_BLOCK), 0, D.s(), pairs_a, m, (zc::u32)nb, (zc::u32)((size_t)W << (c - 1)), (zc::u32)n);
+        const MsmReduceBufs rb{pairs_a, cached, rec_words, bp.affine, m, nb, buckets, present, {ekeys[0], ekeys[1]}, {erecs[0], erecs[1]}, c, bp.TE};
+        u64* sums = nullptr;
+        if (int rc = msm_reduce_windows(D, rb, 0, (int)nw, bp.T, bp.nl0, 0, nullptr, nullptr, 0, D.s(), nullptr, bp.seg, bp.nseg,
+                                        (size_t)ZC_MSM_SEG_QUAD, seg_out, fold_b, &sums))
+            return rc;
+        // Horner's rule over every instance's W window sums at once: 16 instances per 64-lane workgroup
+        hipLaunchKernelGGL(zc::k_msm_window_combine_batch, dim3((unsigned)((batch + 15) / 16)), dim3(64), 0, D.s(), (const u64*)sums, out, batch, W, c);
+        *result = out;
+        HIP_TRY(hipGetLastError());
+    }
+    return ZC_OK;
 }
 
 const uint64_t IDENT_POINT[20] = {0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -2168,6 +2315,83 @@ int zc_msm_fixed_plan(zc_ctx* ctx, size_t n, int window_bits, int32_t* out, int 
     const MsmFixedPlan p = msm_fixed_plan(n, c, 1, ctx->devs[0].tune);
     const size_t mib = (n * (size_t)W * ZC_MSM_REC_STRIDE + ((size_t)1 << 20) - 1) >> 20;
     const int32_t v[8] = {c, W, ZC_MSM_REC_STRIDE, p.T, p.seg, p.sort.passes, (int32_t)mib, 1};
+    memcpy(out, v, sizeof v);
+    return ZC_OK;
+}
+
+// ---- batched variable-base MSM: many independent sums, each over its own points
+
+// out_points[b] = sum_i k[b][i] P[b][i]: one pipeline over the whole batch (msm_batch_on_device), or zc_msm's own path for one
+// instance.  Inputs host (staged, device slot 0) or both on one device of the context; synchronous.
+int zc_msm_batch(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, size_t n, size_t batch, uint64_t* out_points)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (batch == 0) return ZC_OK;
+    REQUIRE(points); REQUIRE(scalars); REQUIRE(out_points);
+    if (n == 0) {
+        for (size_t b = 0; b < batch; b++) memcpy(out_points + 20 * b, IDENT_POINT, sizeof IDENT_POINT);
+        return ZC_OK;
+    }
+    if (int rc = msm_batch_check(n, batch, ctx->devs[0].tune, "zc_msm_batch")) return rc;
+    Residency rp, rk;
+    int dp = -1, dk = -1;
+    residency_of(points, &rp, &dp);
+    residency_of(scalars, &rk, &dk);
+    if (rp != rk || (rp == RES_DEVICE && dp != dk)) return fail(ZC_ERR_MIXED_MEM, "zc_msm_batch: points/scalars residency differs");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DevState* ds = &ctx->devs[0];
+    if (rp == RES_DEVICE) {
+        ds = dev_state_of(ctx, dp);
+        if (!ds) return fail(ZC_ERR_MIXED_MEM, "zc_msm_batch: device buffers do not belong to a device of this context");
+    }
+    DevState& D = *ds;
+    const bool on_device = rp == RES_DEVICE;
+    const u64* res = nullptr;
+    if (batch == 1) {
+        if (int rc = msm_shard(D, points, scalars, n, on_device, &res)) return rc;
+    } else {
+        if (int rc = ring_check(D)) return rc;
+        HIP_TRY(hipSetDevice(D.device));
+        const u64 *dP = points, *dK = scalars;
+        const size_t cnt = n * batch;
+        if (!on_device) {
+            if (int rc = ensure(&D.scratch[0], &D.scratch_bytes[0], cnt * 160)) return rc;
+            if (int rc = ensure(&D.scratch[1], &D.scratch_bytes[1], cnt * 40)) return rc;
+            HIP_TRY(hipMemcpyAsync(D.scratch[0], points, cnt * 160, hipMemcpyHostToDevice, D.s()));
+            HIP_TRY(hipMemcpyAsync(D.scratch[1], scalars, cnt * 40, hipMemcpyHostToDevice, D.s()));
+            dP = (const u64*)D.scratch[0];
+            dK = (const u64*)D.scratch[1];
+        }
+        if (int rc = msm_batch_on_device(D, dP, dK, n, batch, &res)) return rc;
+    }
+    HIP_TRY(hipSetDevice(D.device));
+    HIP_TRY(hipMemcpyAsync(out_points, res, batch * 160, hipMemcpyDeviceToHost, D.s()));
+    HIP_TRY(hipStreamSynchronize(D.s()));
+    return ZC_OK;
+}
+
+// What zc_msm_batch would do for `batch` instances of n pairs -- a query, no device work.  Writes min(nout, 8) entries
+// (nout >= 8): [0] regime (0 = scalar multiplications + folds, 1 = buckets), [1] window bits c, [2] windows W, [3] 1 = affine
+// records, [4] run length of the bucket-sum kernel, [5] buckets per reduction segment, [6] sort passes, [7] record stride in
+// bytes.  One instance reports zc_msm's plan (the call takes zc_msm's path).  Fails where zc_msm_batch fails on its limits.
+int zc_msm_batch_plan(zc_ctx* ctx, size_t n, size_t batch, int points_aligned16, int32_t* out, int nout)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    REQUIRE(out);
+    if (nout < 8) return fail(ZC_ERR_BAD_ARG, "zc_msm_batch_plan: nout < 8");
+    const Tuning& tune = ctx->devs[0].tune;
+    if (int rc = msm_batch_check(n, batch, tune, "zc_msm_batch_plan")) return rc;
+    int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (batch == 1) {
+        const MsmPlan p = msm_plan(n, points_aligned16 != 0, tune);
+        if (p.bad_groups) return fail(ZC_ERR_BAD_ARG, "zc_msm_batch_plan: ZC_MSM_GROUPS does not add up to this shard's window count");
+        const int32_t w[8] = {p.buckets ? 1 : 0, p.c, p.W, p.affine ? 1 : 0, p.buckets ? p.gT[0] : 0, p.seg, p.sort.passes, p.buckets ? p.rec_bytes : 0};
+        memcpy(v, w, sizeof v);
+    } else {
+        const MsmBatchPlan p = msm_batch_plan(n, batch, points_aligned16 != 0, tune);
+        const int32_t w[8] = {p.buckets ? 1 : 0, p.c, p.W, p.affine ? 1 : 0, p.T, p.seg, p.sort.passes, p.buckets ? p.rec_bytes : 0};
+        memcpy(v, w, sizeof v);
+    }
     memcpy(out, v, sizeof v);
     return ZC_OK;
 }

@@ -464,6 +464,32 @@ class Engine:
         return {"window_bits": v[0], "windows": v[1], "record_stride": v[2], "run": v[3], "segment_buckets": v[4],
                 "sort_passes": v[5], "table_mib": v[6], "window_groups": v[7]}
 
+    def msm_batch(self, points, scalars):
+        """`batch` independent MSMs (zc_msm_batch): (batch, n, 20) points and (batch, n, 5) scalars -- numpy, or torch tensors
+        on one device of this context -- give a (batch, 20) numpy array, row b = sum_i scalars[b, i] * points[b, i]."""
+        ps, ks = tuple(points.shape), tuple(scalars.shape)
+        assert len(ps) == 3 and ps[2] == 20 and ks == ps[:2] + (5,), (ps, ks)
+        batch, n = ps[0], ps[1]
+        ptrs = []
+        for a in (points, scalars):
+            if _is_torch(a):
+                assert a.is_contiguous() and a.element_size() == 8
+                self._follow_torch_stream(a)
+                ptrs.append((a, a.data_ptr()))
+            else:
+                a = np.ascontiguousarray(a, dtype=np.uint64)
+                ptrs.append((a, a.ctypes.data))
+        out = np.empty((batch, 20), dtype=np.uint64)
+        self._call("zc_msm_batch", ptrs[0][1], ptrs[1][1], n, batch, out.ctypes.data)
+        return out
+
+    def msm_batch_plan(self, n, batch, points_aligned16=True):
+        """What zc_msm_batch would do for `batch` instances of n pairs (a query, no device work)."""
+        v = (C.c_int32 * 8)()
+        self._call("zc_msm_batch_plan", int(n), int(batch), 1 if points_aligned16 else 0, v, 8)
+        return {"regime": "buckets" if v[0] else "scalar_mul", "window_bits": v[1], "windows": v[2], "affine": bool(v[3]),
+                "run": v[4], "segment_buckets": v[5], "sort_passes": v[6], "record_stride": v[7]}
+
     # ---- the exchange step of a sharded MSM (BASELINE configs[4])
     def msm_partial(self, points, scalars, out=None):
         """This device's sum left in device memory: a (1, 20) int64 torch CUDA tensor (asynchronous)."""

@@ -639,6 +639,33 @@ inline std::array<int32_t, 17> msm_plan(size_t n, bool points_aligned16 = true)
     Backend::check(zc_msm_plan(Backend::ctx(), n, points_aligned16 ? 1 : 0, v.data(), 17), "zc_msm_plan");
     return v;
 }
+// `batch` independent MSMs, each over its own points (zc_msm_batch): pss[b] and kss[b] of one length n for every instance
+// (pad ragged instances with zero scalars); result b equals msm(pss[b], kss[b]) under ==
+inline std::vector<EdwardsPoint> msm_batch(const std::vector<std::vector<EdwardsPoint>>& pss, const std::vector<std::vector<Scalar>>& kss)
+{
+    if (pss.size() != kss.size()) throw std::invalid_argument("msm_batch: size mismatch");
+    const size_t batch = pss.size(), n = batch ? pss[0].size() : 0;
+    std::vector<uint64_t> p(batch * n * 20), k(batch * n * 5), o(batch * 20);
+    for (size_t b = 0; b < batch; b++) {
+        if (pss[b].size() != n || kss[b].size() != n) throw std::invalid_argument("msm_batch: instances of different lengths");
+        for (size_t i = 0; i < n; i++) {
+            pss[b][i].flat(&p[20 * (b * n + i)]);
+            std::memcpy(&k[5 * (b * n + i)], kss[b][i].l.data(), 40);
+        }
+    }
+    Backend::check(zc_msm_batch(Backend::ctx(), p.data(), k.data(), n, batch, o.data()), "zc_msm_batch");
+    std::vector<EdwardsPoint> out(batch);
+    for (size_t b = 0; b < batch; b++) out[b] = EdwardsPoint::unflat(&o[20 * b]);
+    return out;
+}
+// {regime (0 = scalar multiplications + folds, 1 = buckets), c, W, affine, run length, segment buckets, sort passes, record
+// stride bytes} of a batch of `batch` instances of n pairs
+inline std::array<int32_t, 8> msm_batch_plan(size_t n, size_t batch, bool points_aligned16 = true)
+{
+    std::array<int32_t, 8> v{};
+    Backend::check(zc_msm_batch_plan(Backend::ctx(), n, batch, points_aligned16 ? 1 : 0, v.data(), 8), "zc_msm_batch_plan");
+    return v;
+}
 // A fixed-base MSM table (zc_msm_bases_create), freed when the object goes: msm() of one or many scalar vectors against the
 // same bases, each result equal to msm(bases, ks) under ==
 class MsmBases {

@@ -293,6 +293,23 @@ int zc_msm_bases_destroy(zc_ctx *ctx, uint64_t id);
 int zc_msm_fixed(zc_ctx *ctx, uint64_t id, const uint64_t *scalars, size_t batch, uint64_t *out_points);
 int zc_msm_fixed_plan(zc_ctx *ctx, size_t n, int window_bits, int32_t *out, int nout);
 
+/* ---- batched variable-base MSM (additive to ABI 0.6): many independent sums, each over its own points --------------- */
+/* For batches of small MSMs whose bases differ per instance: proof or signature batches, two-term checks s*B - c*A, Pedersen
+ * vector commitments over per-instance bases.  Ragged batches: pad every instance to the longest with zero scalars.
+ *   zc_msm_batch       out_points[b] = sum_i k[b][i] * P[b][i] for b < batch, each equal under == to the reference's sum of
+ *                      `&P[b][i] * &k[b][i]`, like zc_msm; the limbs are deterministic.  points: batch x n x 20 limbs, scalars:
+ *                      batch x n x 5, instance-major (instance b owns rows [b n, (b + 1) n)); both in HOST memory (run on device
+ *                      slot 0) or both on one device of the context, else ZC_ERR_MIXED_MEM.  out_points: HOST, batch x 20.
+ *                      batch == 0: ZC_OK, nothing written; n == 0: batch identities.  ZC_ERR_BAD_ARG, before anything is
+ *                      allocated, when batch*n >= 2^31, batch*n*W >= 2^32 or batch*W*2^(c-1) >= 2^32 (c, W: the window
+ *                      width and count zc_msm_batch_plan reports).  Synchronous; interleaves freely with zc_msm and zc_msm_fixed.
+ *   zc_msm_batch_plan  a query, no device work: writes min(nout, 8) entries (nout >= 8): {regime (0 = scalar multiplications +
+ *                      a fold per instance, 1 = buckets), c, W, affine records, run length, segment buckets, sort passes, record
+ *                      stride bytes}; fails with ZC_ERR_BAD_ARG exactly where zc_msm_batch fails on its limits.              */
+int zc_msm_batch(zc_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t n, size_t batch,
+                 uint64_t *out_points);
+int zc_msm_batch_plan(zc_ctx *ctx, size_t n, size_t batch, int points_aligned16, int32_t *out, int nout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -656,6 +656,31 @@ impl HipBackend {
         Ok(v)
     }
 
+    /// `batch` independent MSMs, each over its own points (`zc_msm_batch`): `ps[b]` and `ks[b]` of one length n for every
+    /// instance (pad ragged instances with zero scalars); result `b` equals `msm(&ps[b], &ks[b])` under `==`.
+    pub fn msm_batch(&self, ps: &[Vec<EdwardsPoint>], ks: &[Vec<Scalar>]) -> Result<Vec<EdwardsPoint>> {
+        assert_eq!(ps.len(), ks.len());
+        let n = ps.first().map_or(0, |p| p.len());
+        let mut fp = Vec::with_capacity(ps.len() * n * 20);
+        let mut fk = Vec::with_capacity(ps.len() * n * 5);
+        for (p, k) in ps.iter().zip(ks) {
+            assert!(p.len() == n && k.len() == n);
+            fp.extend(flat_ed(p));
+            fk.extend(flat_sc(k));
+        }
+        let mut out = vec![0u64; 20 * ps.len()];
+        check(unsafe { ffi::zc_msm_batch(self.ctx, fp.as_ptr(), fk.as_ptr(), n, ps.len(), out.as_mut_ptr()) })?;
+        Ok(unflat_ed(&out))
+    }
+
+    /// What `msm_batch` would do for `batch` instances of `n` pairs (a query, no device work): `[regime (0 = scalar
+    /// multiplications + folds, 1 = buckets), c, W, affine, run length, buckets per segment, sort passes, record stride]`.
+    pub fn msm_batch_plan(&self, n: usize, batch: usize, points_aligned16: bool) -> Result<[i32; 8]> {
+        let mut v = [0i32; 8];
+        check(unsafe { ffi::zc_msm_batch_plan(self.ctx, n, batch, points_aligned16 as i32, v.as_mut_ptr(), 8) })?;
+        Ok(v)
+    }
+
     // -------------------------------------------------------------- sharded MSM: the exchange step
     /// This device's partial sum, left in device memory (`out_dev`: 160 bytes of HIP memory).
     pub unsafe fn msm_partial(&self, points: *const u64, scalars: *const u64, n: usize, out_dev: *mut u64) -> Result<()> {

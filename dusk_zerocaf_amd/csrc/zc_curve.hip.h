@@ -795,6 +795,134 @@ ZC_DI pt scalar_mul_unified(const pt& P, const u32* __restrict__ sk, int stride,
     return ptm_to_pt(Q);
 }
 
+// ---- the doubling/generic ("D/G") schedule of the persistent strict kernel ------------------------------------
+// Two thirds of a lane's formula evaluations are doublings N + N.  For a point that satisfies BOTH
+//   -X^2 + Y^2 = Z^2 + d T^2   and   T Z = X Y          (identities mod p, no division: Z = 0 rows count when they hold)
+// the unified formula at N + N has G = D + C = Z^2 + d T^2 = (Y - X)(Y + X), so C = d T^2 (two multiplications) is not
+// needed: three squarings and five multiplications instead of nine multiplications, T is not read, and every intermediate
+// (M, P, D, E, H, F, G) is the same residue as in ptm_add(n, n) -- the canonicalised outputs are the same limbs.  The unified
+// formula preserves both identities, so checking the loaded point once covers every iterate.
+// Operand classes: Ym < 7N normalized and Yp < 6N lazy are squaring operands (limbs < 2^30, top limb < 2^25); M, P, G < 2N
+// (49/512 N + N); 2D - G + 4N < 7N normalized.
+ZC_DI ptm ptm_double_valid(const ptm& n)
+{
+    const fe M = mont_sqr<FP>(n.Ym);
+    const fe P = mont_sqr<FP>(n.Yp);
+    const fe D = mont_sqr<FP>(n.Z);
+    const fe G = mont_mul<FP>(n.Ym, n.Yp);
+    const fe E = fe_sub_half<FP>(P, M);
+    const fe H = fe_sub_lazy<FP>(P, E);
+    const fe F = fp_sub(fe_add(D, D), G);
+    const fe X3 = mont_mul<FP>(E, F), Y3 = mont_mul<FP>(G, H);
+    ptm r;
+    r.Ym = fp_sub(Y3, X3);
+    r.Yp = fe_add(Y3, X3);
+    r.Z = mont_mul<FP>(F, G);
+    r.T = mont_mul<FP>(E, H);
+    return r;
+}
+// The gate of ptm_double_valid: do both identities hold for the loaded point (n = ptm_from_pt(p))?  Seven multiplications,
+// once per element.
+ZC_DI bool pt_doubling_identities_hold(const pt& p, const ptm& n)
+{
+    const fe lhs = mont_mul<FP>(n.Ym, n.Yp);                                             // Y^2 - X^2
+    const fe rhs = fe_add(mont_sqr<FP>(p.Z), mont_mul<FP>(fe_const<FP>(ModP::D_M), mont_sqr<FP>(p.T)));
+    return fp_eq(rhs, lhs) && fp_eq(mont_mul<FP>(p.T, p.Z), mont_mul<FP>(p.X, p.Y));
+}
+// ptm_add(lhs, rhs) with rhs = N, or the lane's stashed addend read coordinate by coordinate next to the multiplication
+// that consumes it (never a fourth live point; every lane reads its slot, no branch).
+// STASH: fe get(int coordinate) / void put(int coordinate, const fe&), coordinates 0..3 = Ym, Yp, Z, T.
+template <class STASH>
+ZC_DI ptm ptm_add_stash(const ptm& lhs, const ptm& N, bool from_stash, const STASH& S)
+{
+    const fe M = mont_mul<FP>(lhs.Ym, fe_select(from_stash, S.get(0), N.Ym));
+    const fe P = mont_mul<FP>(lhs.Yp, fe_select(from_stash, S.get(1), N.Yp));
+    const fe C = mont_mul<FP>(mont_mul<FP>(fe_const<FP>(ModP::D_M), lhs.T), fe_select(from_stash, S.get(3), N.T));
+    const fe D = mont_mul<FP>(lhs.Z, fe_select(from_stash, S.get(2), N.Z));
+    const fe E = fe_sub_half<FP>(P, M);
+    const fe H = fe_sub_lazy<FP>(P, E);
+    const fe F = fe_sub_lazy<FP>(D, C);
+    const fe G = fe_add(D, C);
+    const fe X3 = mont_mul<FP>(E, F), Y3 = mont_mul<FP>(G, H);
+    ptm o;
+    o.Ym = fp_sub(Y3, X3);
+    o.Yp = fe_add(Y3, X3);
+    o.Z = mont_mul<FP>(F, G);
+    o.T = mont_mul<FP>(E, H);
+    return o;
+}
+// Per-lane state of the schedule.  A lane performs exactly double_and_add's operations in its order -- Q += N_i for the set
+// bits i ascending, N_i the i-th iterate of `self + self`, the first addition identity + N literal, the final doubling skipped
+// -- but an addition may wait in the lane's one stash slot S while N moves on:
+//   G-step (generic formula; every active lane performs ONE operation): a stashed addend first (Q += S), else the pending
+//           addition of bit `pos` (Q += N), else the doubling (N += N).
+//   D-step (ptm_double_valid; wave-uniform): every active lane doubles; a lane whose bit `pos` is still pending stores N to S
+//           first.
+// A wave alternates: after every G-step (no lane has anything stashed then) a D-step follows iff no active lane is at its top
+// bit (sm_tile_wants_d_step on that ballot).  A lane at its top bit retires within the next G-step or two, the others'
+// doublings riding along in the generic formula; letting such lanes sit out D-steps instead saves no step in the model.
+// With D-steps switched off (a tile with a lane that fails the gate) nothing is ever stashed and the G-steps alone are
+// scalar_mul_unified's loop.
+// tools/sm_schedule_model.py is this schedule on the CPU (steps per tile, instruction-count ratio).
+struct sm_lane {
+    int pos, nbits;
+    u32 cur;              // scalar word that holds bit `pos`
+    bool taken;           // the addition for bit `pos` has been performed or stashed
+    bool has_stash;
+    bool active;
+};
+ZC_DI sm_lane sm_lane_init(const u32* __restrict__ sk, int nbits)
+{
+    sm_lane L;
+    L.pos = 0;
+    L.nbits = nbits;
+    L.cur = sk[0];
+    L.taken = false;
+    L.has_stash = false;
+    L.active = nbits > 0;
+    return L;
+}
+ZC_DI bool sm_bit_pending(const sm_lane& L) { return ((L.cur >> (L.pos & 31)) & 1) != 0 && !L.taken; }
+ZC_DI bool sm_at_top(const sm_lane& L) { return L.active && L.pos >= L.nbits - 1; }
+ZC_DI bool sm_tile_wants_d_step(bool any_active, bool any_at_top) { return any_active && !any_at_top; }     // right after a G-step
+ZC_DI void sm_lane_advance(sm_lane& L, const u32* __restrict__ sk, int stride)
+{
+    L.pos++;
+    if ((L.pos & 31) == 0) L.cur = sk[(L.pos >> 5) * stride];
+    L.taken = false;
+}
+template <class STASH>
+ZC_DI void sm_g_step(sm_lane& L, ptm& N, ptm& Q, const STASH& S, const u32* __restrict__ sk, int stride)
+{
+    if (!L.active) return;
+    const bool from_stash = L.has_stash;
+    const bool add = from_stash || sm_bit_pending(L);
+    const ptm r = ptm_add_stash(ptm_select(add, Q, N), N, from_stash, S);
+    if (add) {
+        Q = r;
+        if (!from_stash) L.taken = true;
+        L.has_stash = false;
+    } else {
+        N = r;
+        sm_lane_advance(L, sk, stride);
+    }
+    L.active = L.pos < L.nbits - 1 || !L.taken;                     // the top bit is set: its addition retires the lane
+}
+template <class STASH>
+ZC_DI void sm_d_step(sm_lane& L, ptm& N, STASH& S, const u32* __restrict__ sk, int stride)
+{
+    if (!L.active) return;                                           // (no active lane is at its top bit, nothing is stashed)
+    if (sm_bit_pending(L)) {
+        S.put(0, N.Ym);
+        S.put(1, N.Yp);
+        S.put(2, N.Z);
+        S.put(3, N.T);
+        L.has_stash = true;
+    }
+    N = ptm_double_valid(N);
+    sm_lane_advance(L, sk, stride);
+}
+
 // Left-to-right variants of the reference, same unified-step machinery with
 // Q = Q + Q or Q = Q + (+-P):
 //   MODE 1  ltr_bin_mul     (edwards.rs:122-134): for i = 248..0 { Q = 2Q; if bit_i: Q += P }

@@ -813,8 +813,64 @@ ZC_KERNEL void k_ed_scalar_mul(const u64* p, const u64* k, size_t k_stride, u64*
 // Records are gathered through the permutation (160-byte points, 40-byte scalars: whole-line
 // gathers roughly double the 210 MB read per 2^20, still ~0.3 % of the HBM roof).  Scalar words live
 // in the wave's own 9 x 64-word LDS region; LDS operations of one wave execute in order, so no
-// barrier is needed anywhere.  Results are the same limbs as k_ed_scalar_mul's (same per-lane loop).
+// barrier is needed anywhere.  Results are the same limbs as k_ed_scalar_mul's (same per-lane operations).
+// The wave's stash slots (one addend per lane, 36 words) in its own LDS region, word j of a lane at s[64 j]: every access is
+// conflict-free and, like the scalar words, needs no barrier.
+struct sm_stash_lds {
+    u32* s;
+    ZC_DI fe get(int c) const
+    {
+        fe r;
+#pragma unroll
+        for (int i = 0; i < 9; i++) r.v[i] = s[64 * (9 * c + i)];
+        return r;
+    }
+    ZC_DI void put(int c, const fe& x) const
+    {
+#pragma unroll
+        for (int i = 0; i < 9; i++) s[64 * (9 * c + i)] = x.v[i];
+    }
+};
+// The D/G schedule (zc_curve.hip.h: sm_lane): the per-lane operations are scalar_mul_unified's, but a wave alternates generic
+// steps with wave-uniform doubling steps of 3 squarings + 5 multiplications (ptm_double_valid), a lane's pending addition
+// waiting in its stash slot meanwhile -- about half the steps of a tile are doubling steps.  The branch decision comes from
+// ballots, so neither multiplication body runs divergent.  A tile with a lane whose point fails the gate of
+// ptm_double_valid (off the curve, or T Z != X Y) runs generic steps only: exactly scalar_mul_unified's schedule.
+// LDS: (9 + 36) words x 256 lanes = 45 KB per workgroup, three workgroups per CU.
 ZC_KERNEL void k_ed_scalar_mul_pw(const u64* p, const u64* k, u64* out, const u32* idx, u32* counter, u32 n)
+{
+    __shared__ u32 sk[9 * ZC_BLOCK];
+    __shared__ u32 st[36 * ZC_BLOCK];
+    const int lane = threadIdx.x & 63;
+    u32* skw = sk + 9 * (threadIdx.x & ~63) + lane;        // word j of this lane: skw[64 j]
+    sm_stash_lds S;
+    S.s = st + 36 * (threadIdx.x & ~63) + lane;
+    const u32 ntiles = (n + 63) / 64;
+    for (;;) {
+        u32 t = 0;
+        if (lane == 0) t = atomicAdd(counter, 1u);
+        t = (u32)__builtin_amdgcn_readfirstlane((int)t);
+        if (t >= ntiles) break;
+        const u32 i = t * 64 + lane;
+        const bool valid = i < n;
+        const size_t own = valid ? (size_t)idx[i] : 0;
+        u64 l[5];
+        load_scalar(l, k + 5 * own);
+        int nbits;
+        scalar_to_words(skw, 64, l, nbits);
+        const pt P = pt_load(p + 20 * own);
+        ptm N = ptm_from_pt(P), Q = ptm_from_pt(pt_identity());
+        const bool d_ok = wave_all(!valid || pt_doubling_identities_hold(P, N));
+        sm_lane L = sm_lane_init(skw, valid ? nbits : 0);
+        while (wave_any(L.active)) {
+            sm_g_step(L, N, Q, S, skw, 64);
+            if (d_ok && sm_tile_wants_d_step(wave_any(L.active), wave_any(sm_at_top(L)))) sm_d_step(L, N, S, skw, 64);
+        }
+        if (valid) pt_store(out + 20 * own, ptm_to_pt(Q));
+    }
+}
+// The unified-step schedule on the same persistent waves (every step the generic formula): ZC_SCHED=unified.
+ZC_KERNEL void k_ed_scalar_mul_pw_unified(const u64* p, const u64* k, u64* out, const u32* idx, u32* counter, u32 n)
 {
     __shared__ u32 sk[9 * ZC_BLOCK];
     const int lane = threadIdx.x & 63;

@@ -59,6 +59,7 @@ constexpr int MAX_ARGS = 6;
 struct Tuning {
     long host_chunks = 0;            // ZC_HOST_CHUNKS=k: host batches move in k chunks
     bool sched_block = false;        // ZC_SCHED=block: one workgroup per 256 elements instead of persistent waves
+    bool sched_unified = false;      // ZC_SCHED=unified: persistent waves on generic steps only (no doubling steps)
     unsigned ring_slots = 0;         // ZC_RING_SLOTS=k (1..512): wave slots per XCD of the windowed core's table ring
     bool ristretto_strict = false;   // ZC_RISTRETTO_STRICT=1: config-4 round trip on the reference's formula sequence
     long inv_chunk = 0;              // ZC_INV_CHUNK=c (1..64): elements per lane sharing one inversion
@@ -92,7 +93,10 @@ Tuning tuning_from_env()
 {
     Tuning t;
     t.host_chunks = env_long("ZC_HOST_CHUNKS", 1, 1 << 20, 0);
-    if (const char* e = getenv("ZC_SCHED")) t.sched_block = std::string(e) == "block";
+    if (const char* e = getenv("ZC_SCHED")) {
+        t.sched_block = std::string(e) == "block";
+        t.sched_unified = std::string(e) == "unified";
+    }
     t.ring_slots = (unsigned)env_long("ZC_RING_SLOTS", 1, 512, 0);
     t.ristretto_strict = env_long("ZC_RISTRETTO_STRICT", 0, 1 << 30, 0) != 0;
     t.inv_chunk = env_long("ZC_INV_CHUNK", 1, 64, 0);
@@ -475,7 +479,8 @@ const zc::u32* balance_index(DevState& D, const u64* k, size_t cnt, zc::u32** co
     return idx;
 }
 // Strict scalar-mul batches from this size on run on persistent waves over the cost-sorted
-// permutation (k_ed_scalar_mul_pw); ZC_SCHED=block keeps one workgroup per 256 elements.
+// permutation (k_ed_scalar_mul_pw: generic steps alternating with wave-uniform doubling steps); ZC_SCHED=unified keeps the
+// persistent waves on generic steps only, ZC_SCHED=block keeps one workgroup per 256 elements.
 constexpr size_t PW_MIN_ELEMS = (size_t)1 << 17;
 
 // Launches of at most one workgroup per CU keep a single wave on every SIMD; a lone wave cannot
@@ -561,7 +566,7 @@ void scalar_mul_on_device(DevState& D, const u64* p, const u64* k, u64* out, siz
     if (cnt >= PW_MIN_ELEMS && !D.tune.sched_block) {
         zc::u32* counter = nullptr;
         if (const zc::u32* perm = balance_index(D, k, cnt, &counter)) {
-            hipLaunchKernelGGL(zc::k_ed_scalar_mul_pw, dim3((unsigned)(3 * D.cus)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, perm, counter, (zc::u32)cnt);
+            hipLaunchKernelGGL(D.tune.sched_unified ? zc::k_ed_scalar_mul_pw_unified : zc::k_ed_scalar_mul_pw, dim3((unsigned)(3 * D.cus)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, perm, counter, (zc::u32)cnt);
             return;
         }
     }

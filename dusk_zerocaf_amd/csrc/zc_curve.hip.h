@@ -1179,6 +1179,7 @@ ZC_DI int scalar_digits16(int8_t* __restrict__ dig, int stride, const u64 (&l)[5
 struct table_ptr {
     u32* p;
     ZC_DI u32* entry(int j) const { return p + 32 * j; }
+    ZC_DI table_ptr term(int t) const { return table_ptr{p + 256 * t}; }      // lincomb_fast: one 1 KB table per term
 };
 template <bool ILP, class TABLE>
 ZC_DI pt fast_window_loop(const TABLE table, const int8_t* __restrict__ dig, int stride, int top)
@@ -1199,6 +1200,22 @@ ZC_DI pt fast_window_loop(const TABLE table, const int8_t* __restrict__ dig, int
     }
     return Q;
 }
+// table[j] = (j + 1) P, cached form:
+// one doubling, then a chain of cached additions of P.  (Two live points instead of the four a
+// doubling tree keeps: the build costs the same 55 multiplications and no longer forces spills.)
+template <class TABLE>
+ZC_DI void fast_table_build(const pt& P, const TABLE table)
+{
+    const niels c1 = niels_from_pt(P);
+    niels_store(table.entry(0), c1);
+    pt q = pt_double_fast<true>(P);
+    niels_store(table.entry(1), niels_from_pt(q));
+#pragma unroll 1
+    for (int j = 2; j < 8; j++) {
+        q = pt_add_cached(q, c1);
+        niels_store(table.entry(j), niels_from_pt(q));
+    }
+}
 // k * P with fixed signed 4-bit windows over a per-lane table {1P..8P} of cached points in
 // global scratch (8 x 128 bytes per point, one cache line per entry).  Uniform control flow:
 // every lane of a wave runs the same schedule from window `top` (wave-uniform) down to 0.
@@ -1207,22 +1224,106 @@ ZC_DI pt fast_window_loop(const TABLE table, const int8_t* __restrict__ dig, int
 template <class TABLE>
 ZC_DI pt scalar_mul_fast(const pt& P, const TABLE table, const int8_t* __restrict__ dig, int stride, int top)
 {
-    // table[j] = (j + 1) P, cached form:
-    // one doubling, then a chain of cached additions of P.  (Two live points instead of the four a
-    // doubling tree keeps: the build costs the same 55 multiplications and no longer forces spills.)
-    {
-        const niels c1 = niels_from_pt(P);
-        niels_store(table.entry(0), c1);
-        pt q = pt_double_fast<true>(P);
-        niels_store(table.entry(1), niels_from_pt(q));
-#pragma unroll 1
-        for (int j = 2; j < 8; j++) {
-            q = pt_add_cached(q, c1);
-            niels_store(table.entry(j), niels_from_pt(q));
-        }
-    }
+    fast_table_build(P, table);
     // small launches (one wave per SIMD) take the independent-chain multiplier, like the strict kernel
     return zc_small_launch() ? fast_window_loop<true>(table, dig, stride, top) : fast_window_loop<false>(table, dig, stride, top);
+}
+
+// ---------------------------------------------------------------- short linear combinations (shared doublings)
+// sum_j k_j * P_j for a handful of terms per lane (Straus): one table {1P_j..8P_j} per term, ONE doubling chain
+// from the top window down and one cached addition per term and window -- 1827 + 567 t multiplications instead
+// of the 2394 t + 9 (t - 1) of t windowed multiplications and a fold.
+constexpr int LINCOMB_MAX_TERMS = 8;
+// The digits are not stored: a scalar is kept as v + 0x88..8 (66 nibbles of 8: nine words), and
+// digit i = nibble i - 8.  Adding 8 to every nibble runs the very carry chain of scalar_digits16 (a nibble plus
+// its carry-in reaches 8 exactly when the sum below overflows into the next nibble), so the digits are the same
+// 66 values in [-8, 8) -- at 36 bytes per scalar instead of 66.  Returns the index of the highest non-zero digit or -1.
+ZC_DI int scalar_recode16(u32* __restrict__ rw, int stride, const u64 (&l)[5])
+{
+    u32 w[9];
+    int nb;
+    scalar_to_words(w, 1, l, nb);
+    u64 c = 0;
+    int top = -1;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const u32 eights = k < 8 ? 0x88888888u : 0x88u;   // v < 2^260 and 66 nibbles of 8: the sum stays below 16^66
+        c += (u64)w[k] + eights;
+        const u32 r = (u32)c;
+        c >>= 32;
+        rw[k * stride] = r;
+        const u32 x = r ^ eights;                         // a nibble of x is zero where the digit is
+        if (x) top = 8 * k + ((31 - __builtin_clz(x)) >> 2);
+    }
+    ZC_ASSERT(c == 0 && top < 66);
+    return top;
+}
+ZC_DI int recoded_digit(const u32* __restrict__ rw, int stride, int i)
+{
+    return (int)((rw[(i >> 3) * stride] >> ((i & 7) * 4)) & 15u) - 8;
+}
+// rw: the terms' recoded scalars, word k of term j at rw[(9 * j + k) * stride].  table.term(j): term j's table.
+template <bool ILP, class TABLE>
+ZC_DI pt lincomb_window_loop(const TABLE table, const u32* __restrict__ rw, int stride, int terms, int top)
+{
+    pt Q = pt_identity();
+    for (int i = top; i >= 0; i--) {
+        if (i != top) {
+            Q = pt_double_fast<false, ILP>(Q);
+            Q = pt_double_fast<false, ILP>(Q);
+            Q = pt_double_fast<false, ILP>(Q);
+            Q = pt_double_fast<true, ILP>(Q);
+        }
+#pragma unroll 1
+        for (int j = 0; j < terms; j++) {
+            const int d = recoded_digit(rw + 9 * j * stride, stride, i);
+            const int mag = d < 0 ? -d : d;
+            niels c = niels_identity();
+            if (mag != 0) c = niels_load(table.term(j).entry(mag - 1));
+            Q = pt_add_cached<ILP>(Q, niels_cond_neg(d < 0, c));
+        }
+    }
+    return Q;
+}
+// points: the row's `terms` consecutive records.  `top`: the highest non-zero digit over the row's terms -- and,
+// in the kernel, over the wave: control flow is uniform, a zero digit adds the cached identity.
+// Like scalar_mul_fast, NOT the reference's formula sequence: the same group element as ((k0 P0 + k1 P1) + ...),
+// a different projective representative, deterministic limbs.
+template <class TABLE>
+ZC_DI pt lincomb_fast(const u64* __restrict__ points, const TABLE table, const u32* __restrict__ rw, int stride, int terms, int top)
+{
+#pragma unroll 1
+    for (int j = 0; j < terms; j++) fast_table_build(pt_load(points + 20 * j), table.term(j));
+    return zc_small_launch() ? lincomb_window_loop<true>(table, rw, stride, terms, top) : lincomb_window_loop<false>(table, rw, stride, terms, top);
+}
+// Does every point of the row satisfy the curve equation and T Z = X Y?  Only then are the dedicated doublings and the
+// re-associated additions the reference's sum as a group element.  A row that fails (the reference's FOUR_COSET_GROUP
+// itself holds the off-curve point (1, 0)) is evaluated again by lincomb_strict, which overwrites lincomb_fast's result.
+ZC_DI bool lincomb_row_on_curve(const u64* __restrict__ points, int terms)
+{
+    bool ok = true;
+#pragma unroll 1
+    for (int j = 0; j < terms; j++) {
+        const pt P = pt_load(points + 20 * j);
+        ok = ok && pt_doubling_identities_hold(P, ptm_from_pt(P));
+    }
+    return ok;
+}
+// The reference's own sequence for one row: double_and_add per term, folded with the unified addition in index order.
+// sk: nine words of scratch for the scalar's bits, word w at sk[w * stride].
+ZC_DI pt lincomb_strict(const u64* __restrict__ points, const u64* __restrict__ scalars, int terms, u32* __restrict__ sk, int stride)
+{
+    pt acc = pt_identity();
+#pragma unroll 1
+    for (int j = 0; j < terms; j++) {
+        u64 l[5];
+        load_scalar(l, scalars + 5 * j);
+        int nbits;
+        scalar_to_words(sk, stride, l, nbits);
+        const pt q = scalar_mul_unified(pt_load(points + 20 * j), sk, stride, nbits);
+        acc = j ? pt_add(acc, q) : q;
+    }
+    return acc;
 }
 
 // ---------------------------------------------------------------- byte codecs

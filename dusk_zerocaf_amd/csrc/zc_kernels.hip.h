@@ -1035,6 +1035,67 @@ ZC_KERNEL_3W void k_ed_scalar_mul_fast(const u64* p, const u64* k, u32 k_stride,
     ring_release(ring, hold + (threadIdx.x >> 6));
     if (valid) pt_store(out + 20 * (size_t)i, Q);
 }
+// ---- short linear combinations per row: out[i] = sum_j k[i][j] * P[i][j], shared doublings (lincomb_fast) ----------
+// A wave's slot is `slot_units` consecutive 64 KB units of the ring's table area, one per term (lane l's table of term j:
+// unit j, [l KB, (l + 1) KB)); the XCDs' areas are `units_per_xcd` units apart.  The slot is taken and given back through
+// ring_acquire / ring_release as they are: the host passes slots <= units_per_xcd / slot_units, ring_acquire names
+// (xcc, slot) through the single-unit address it returns, and the kernel re-bases that pair on its own geometry.  The
+// flags stay at xcc * RING_SLOTS + slot (slots <= RING_SLOTS).
+// Scalars are kept recoded in LDS, nine words per term and lane (scalar_recode16): 36 * terms bytes per lane, dynamic.
+// The host launches five and more terms with 128-lane workgroups so that a workgroup's LDS stays below 37 KB and four to
+// six of them fit a CU; the stride of the LDS arrays is the workgroup size.
+struct ring_table_terms {
+    u32* base;
+    ZC_DI ring_table term(int t) const { return ring_table{base + (size_t)t * (64 * 256)}; }
+};
+ZC_KERNEL_3W void k_ed_lincomb(const u64* p, const u64* k, u32 terms, u64* out, u32* table, u32* ring, u32 ring_slots,
+                               u32 units_per_xcd, u32 slot_units, u32 n)
+{
+    extern __shared__ u32 lincomb_rw[];                    // 9 * terms * blockDim.x words
+    const int tid = threadIdx.x, block = blockDim.x;
+    const u32 wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 i = blockIdx.x * block + tid;
+    const bool valid = i < n;
+    const size_t first = (size_t)(valid ? i : 0) * terms;  // the row's first record (n * terms < 2^31)
+    int top = -1;
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) {
+        u64 l[5];
+        load_scalar(l, k + 5 * (first + j));
+        const int tj = scalar_recode16(lincomb_rw + 9 * j * block + tid, block, l);
+        top = tj > top ? tj : top;
+    }
+    if (!valid) top = -1;
+    top = wave_max_small(top);
+    __shared__ u32 hold[ZC_BLOCK / 64];
+    const ring_table got = ring_acquire(table, ring, hold + wave_in_block, ring_slots);
+    if (!got.base) {                                       // the wave gave up waiting for its table slot (wave-uniform): poison, no barrier follows
+        if (valid)
+            for (int j = 0; j < 20; j++) out[20 * (size_t)i + j] = ~(u64)0;
+        return;
+    }
+    const u32 named = (u32)((size_t)(got.base - table) / (64 * 256));          // xcc * RING_SLOTS + slot (wave-uniform)
+    const u32 xcc = named / RING_SLOTS, slot = named % RING_SLOTS;
+    const ring_table_terms mine{table + (size_t)(xcc * units_per_xcd + slot * slot_units) * (64 * 256)};
+    const pt Q = lincomb_fast(p + 20 * first, mine, lincomb_rw + tid, block, (int)terms, top);
+    ring_release(ring, hold + wave_in_block);
+    const u32 i_late = blockIdx.x * block + wave_in_block * 64u + lane_id_fresh();
+    if (i_late < n) pt_store(out + 20 * (size_t)i_late, Q);
+}
+// Second pass of zc_ed_lincomb, behind k_ed_lincomb on the stream: rows that hold a point off the curve (or with T Z != X Y)
+// are evaluated again with the reference's own formula sequence and overwritten -- on such inputs the unified formula is
+// no group law and no other schedule reproduces it.  A pass of its own so that the windowed kernel keeps its register
+// budget: it reads the points once more (160 bytes per term) and spends six multiplications per term on the test,
+// under 1 % of the call; the strict branch is practically never taken.
+ZC_KERNEL void k_ed_lincomb_off_curve_rows(const u64* p, const u64* k, u32 terms, u64* out, u32 n)
+{
+    __shared__ u32 sk[9 * ZC_BLOCK];
+    const u32 i = blockIdx.x * ZC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const size_t first = (size_t)i * terms;
+    if (lincomb_row_on_curve(p + 20 * first, (int)terms)) return;
+    pt_store(out + 20 * (size_t)i, lincomb_strict(p + 20 * first, k + 5 * first, (int)terms, sk + threadIdx.x, ZC_BLOCK));
+}
 // fused config-4 path on the fast core: the boundary is bytes in / bytes out, and a Ristretto
 // encoding depends only on the group element, so the outputs stay bit-identical to the reference
 ZC_KERNEL_3W void k_ris_roundtrip_mul_fast(const uint8_t* in, const u64* k, uint8_t* out, uint8_t* ok, u32* table, u32* ring, u32 ring_slots, u32 n)

@@ -500,11 +500,23 @@ inline strict_kernel_t strict_kernel_for(size_t cnt)
 // beyond 2^31 elements the batch goes in pieces, one after the other on the stream).
 // launch(table, ring_state, slots_per_xcd, offset, count).  ZC_RING_SLOTS=k (1..512) shrinks the ring so that
 // waves really wait for one another (tests; the default leaves more slots than waves fit an XCD).
+// zc_ed_lincomb takes `slot_units` consecutive 64 KB units per wave slot, one per term (zc_kernels.hip.h: k_ed_lincomb).
+// The table area then grows with the slot, up to LINCOMB_MAX_UNITS units per XCD (1 GB in all): 512 slots up to four terms,
+// then 409, 341, 292, 256 for five to eight.  Waves of that kernel resident per XCD: 384 up to five terms, then 320, 320,
+// 256 (LDS-bound) -- so the ring has a free slot for every resident wave except at seven terms, where up to 28 waves per
+// XCD queue for one (by the ring's own protocol).  The single-unit kernels address the first 256 MB of the area whatever
+// its size (their XCD stride stays RING_SLOTS units).
 constexpr size_t FAST_MAX_LAUNCH = (size_t)1 << 31;
-template <class L>
-int fast_ring(DevState& D, size_t cnt, L&& launch)
+constexpr size_t LINCOMB_MAX_UNITS = 2048;
+inline size_t ring_units_per_xcd(size_t slot_units)
 {
-    int rc = ensure(&D.fast, &D.fast_bytes, zc::RING_TABLE_BYTES);
+    return slot_units <= 1 ? (size_t)zc::RING_SLOTS : std::min((size_t)zc::RING_SLOTS * slot_units, LINCOMB_MAX_UNITS);
+}
+template <class L>
+int fast_ring(DevState& D, size_t cnt, L&& launch, size_t slot_units = 1)
+{
+    const size_t units_per_xcd = ring_units_per_xcd(slot_units);
+    int rc = ensure(&D.fast, &D.fast_bytes, zc::RING_TABLE_BYTES / zc::RING_SLOTS * units_per_xcd);
     if (rc) return rc;
     if (!D.ring) {
         // The error word lives in pinned HOST memory the device can write (a wave that gives up stores through the
@@ -534,7 +546,7 @@ int fast_ring(DevState& D, size_t cnt, L&& launch)
         D.ring_bytes = zc::RING_ALLOC_WORDS * sizeof(zc::u32);
     }
     // a launch hands out fewer than 2^19 generations of its slots (the 19-bit field of the word ring_acquire parks)
-    const zc::u32 slots = D.tune.ring_slots ? (zc::u32)D.tune.ring_slots : zc::RING_SLOTS;
+    const zc::u32 slots = std::min(D.tune.ring_slots ? (zc::u32)D.tune.ring_slots : zc::RING_SLOTS, (zc::u32)(units_per_xcd / slot_units));
     zc::u32 slots_arg = slots;
 #ifdef ZC_TEST_HOOKS
     slots_arg |= (zc::u32)D.tune.test_ring_spins << 16;      // test build: the kernels take their spin limit from the upper half
@@ -1733,6 +1745,30 @@ int zc_ed_scalar_mul(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t
     if (flags == ZC_SCALAR_MUL_LTR_BIN) return binop(ctx, zc::k_ed_scalar_mul_ltr_bin, nullptr, p, k, out, n, 0);
     if (flags == ZC_SCALAR_MUL_BINARY_NAF) return binop(ctx, zc::k_ed_scalar_mul_naf, nullptr, p, k, out, n, 0);
     return fail(ZC_ERR_BAD_ARG, "unknown scalar_mul flags");
+}
+// out[i] = sum_j k[i][j] * P[i][j]: one shared doubling chain per row (zc_curve.hip.h: lincomb_fast)
+int zc_ed_lincomb(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, size_t terms, uint64_t* out, size_t n)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    REQUIRE(points); REQUIRE(scalars); REQUIRE(out);
+    if (terms < 1 || terms > ZC_LINCOMB_MAX_TERMS) return fail(ZC_ERR_BAD_ARG, "zc_ed_lincomb: terms must be 1..ZC_LINCOMB_MAX_TERMS");
+    if (n >= ((size_t)1 << 31) / terms + (((size_t)1 << 31) % terms != 0)) return fail(ZC_ERR_BAD_ARG, "zc_ed_lincomb: n * terms must stay below 2^31");
+    Arg args[3] = {in_arg(points, 160 * terms), in_arg(scalars, 40 * terms), out_arg(out, 160)};
+    int inner = ZC_OK;
+    int rc = run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
+        // five and more terms: 128-lane workgroups keep a workgroup's LDS (36 bytes per lane and term) below 37 KB
+        const unsigned block = terms > 4 ? 128u : (unsigned)zc::ZC_BLOCK;
+        const zc::u32 units = (zc::u32)ring_units_per_xcd(terms);
+        inner = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ed_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * terms * block, D.s(),
+                               (const u64*)d[0] + 20 * terms * off, (const u64*)d[1] + 5 * terms * off, (zc::u32)terms, (u64*)d[2] + 20 * off,
+                               table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
+        }, terms);
+        if (inner == ZC_OK)
+            hipLaunchKernelGGL(zc::k_ed_lincomb_off_curve_rows, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1],
+                               (zc::u32)terms, (u64*)d[2], (zc::u32)cnt);
+    }, true);
+    return rc ? rc : inner;
 }
 int zc_ed_mul_by_pow_2(zc_ctx* ctx, const uint64_t* p, uint64_t kexp, uint64_t* out, size_t n)
 {

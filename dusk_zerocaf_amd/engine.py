@@ -280,6 +280,28 @@ class Engine:
         self._call("zc_ed_scalar_mul", pp, pk, po, n, flags)
         return out
 
+    def ed_lincomb(self, points, scalars):
+        """out[i] = sum_j scalars[i, j] * points[i, j] (zc_ed_lincomb): (n, t, 20) points and (n, t, 5) scalars, t = 1..8 --
+        numpy arrays, or contiguous torch tensors on one device (the call then runs on torch's current stream and the result
+        stays on the device) -> (n, 20) of the same kind.  One doubling chain per row is shared by its terms; the result is
+        the same group element as the composition of ed_scalar_mul and ed_add (ed_eq / encodings), not the same limbs."""
+        tensors = _is_torch(points)
+        assert tensors == _is_torch(scalars), "ed_lincomb: points and scalars must both be numpy arrays or both torch tensors"
+        if not tensors:
+            points, scalars = np.ascontiguousarray(points, dtype=np.uint64), np.ascontiguousarray(scalars, dtype=np.uint64)
+        assert points.ndim == 3 and scalars.ndim == 3 and points.shape[2] == 20 and scalars.shape[2] == 5, (points.shape, scalars.shape)
+        assert tuple(points.shape[:2]) == tuple(scalars.shape[:2]), (points.shape, scalars.shape)
+        n, t = int(points.shape[0]), int(points.shape[1])
+        if tensors:
+            assert points.is_contiguous() and scalars.is_contiguous() and points.element_size() == 8 and scalars.element_size() == 8
+            self._follow_torch_stream(points)
+            pp, pk = points.data_ptr(), scalars.data_ptr()
+        else:
+            pp, pk = points.ctypes.data, scalars.ctypes.data
+        out, po = self._alloc(points, n, 20, np.uint64)
+        self._call("zc_ed_lincomb", pp, pk, t, po, n)
+        return out
+
     def ed_mul_by_pow_2(self, p, kexp):
         p, pp, n = self._prep(p, 20, np.uint64)
         out, po = self._alloc(p, n, 20, np.uint64)

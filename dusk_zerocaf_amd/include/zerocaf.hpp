@@ -658,6 +658,27 @@ inline std::vector<EdwardsPoint> msm_batch(const std::vector<std::vector<Edwards
     for (size_t b = 0; b < batch; b++) out[b] = EdwardsPoint::unflat(&o[20 * b]);
     return out;
 }
+// Short linear combinations, one per row (zc_ed_lincomb): out[i] = sum_j kss[i][j] * pss[i][j], 1..8 terms of one count for
+// every row (pad ragged rows with zero scalars); row i equals ((k0*P0 + k1*P1) + ...) under ==.  One doubling chain per row
+// is shared by its terms: for 2..8 terms per row this is the call, from 64 pairs per instance on msm_batch.
+inline std::vector<EdwardsPoint> ed_lincomb(const std::vector<std::vector<EdwardsPoint>>& pss, const std::vector<std::vector<Scalar>>& kss)
+{
+    if (pss.size() != kss.size()) throw std::invalid_argument("ed_lincomb: size mismatch");
+    const size_t n = pss.size(), t = n ? pss[0].size() : 1;
+    std::vector<uint64_t> p(n * t * 20), k(n * t * 5), o(n * 20);
+    for (size_t i = 0; i < n; i++) {
+        if (pss[i].size() != t || kss[i].size() != t) throw std::invalid_argument("ed_lincomb: rows of different lengths");
+        for (size_t j = 0; j < t; j++) {
+            pss[i][j].flat(&p[20 * (i * t + j)]);
+            std::memcpy(&k[5 * (i * t + j)], kss[i][j].l.data(), 40);
+        }
+    }
+    if (n == 0) return {};
+    Backend::check(zc_ed_lincomb(Backend::ctx(), p.data(), k.data(), t, o.data(), n), "zc_ed_lincomb");
+    std::vector<EdwardsPoint> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = EdwardsPoint::unflat(&o[20 * i]);
+    return out;
+}
 // {regime (0 = scalar multiplications + folds, 1 = buckets), c, W, affine, run length, segment buckets, sort passes, record
 // stride bytes} of a batch of `batch` instances of n pairs
 inline std::array<int32_t, 8> msm_batch_plan(size_t n, size_t batch, bool points_aligned16 = true)

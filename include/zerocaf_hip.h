@@ -310,6 +310,23 @@ int zc_msm_batch(zc_ctx *ctx, const uint64_t *points, const uint64_t *scalars, s
                  uint64_t *out_points);
 int zc_msm_batch_plan(zc_ctx *ctx, size_t n, size_t batch, int points_aligned16, int32_t *out, int nout);
 
+/* ---- short linear combinations per row (additive to ABI 0.6): a*P + b*Q, or a handful of terms, for millions of rows --- */
+/* out[i] = sum_{j < terms} k[i][j] * P[i][j]                                                         (not in the reference)
+ * points: n x terms x 20 limbs, scalars: n x terms x 5, row-major (row i owns `terms` consecutive records).
+ * Each k is a Mul<Scalar> operand (raw limbs, then the rule of double_and_add's loop test, as zc_ed_scalar_mul reads them).
+ * out: n x 20, equal under == (affine / compressed) to the reference's ((k0*P0 + k1*P1) + ...) built from `&P * &k` and `+`;
+ * not limb-identical (same contract as ZC_SCALAR_MUL_FAST); the limbs are deterministic.  One doubling chain per row is
+ * shared by its terms (signed 4-bit windows over per-term tables): 1827 + 567 terms field multiplications per row against
+ * 2394 terms + 9 (terms - 1) for zc_ed_scalar_mul(FAST) per term and zc_ed_add.  A zero scalar costs its table only (pad
+ * ragged rows with zero scalars).
+ * All three arrays in HOST memory (staged in chunks, synchronous like the other element-wise calls) or all on one device of
+ * the context (in place, asynchronous on the context stream), else ZC_ERR_MIXED_MEM.
+ * terms 1..ZC_LINCOMB_MAX_TERMS, else ZC_ERR_BAD_ARG; n == 0: ZC_OK, nothing written; n * terms >= 2^31: ZC_ERR_BAD_ARG
+ * (the call is not cut into launches: split the batch).  Shares the windowed core's table ring (and its failure report,
+ * see zc_last_error above); the ring's table area grows to terms x 256 MB, at most 1 GB, on first use.                      */
+#define ZC_LINCOMB_MAX_TERMS 8
+int zc_ed_lincomb(zc_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t terms, uint64_t *out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

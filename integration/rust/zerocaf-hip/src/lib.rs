@@ -681,6 +681,27 @@ impl HipBackend {
         Ok(v)
     }
 
+    /// Short linear combinations, one per row (`zc_ed_lincomb`): `out[i] = sum_j ks[i][j] * ps[i][j]`, 1..8 terms of one
+    /// count for every row (pad ragged rows with zero scalars); row `i` equals `(k0*P0 + k1*P1) + ...` under `==`.  One
+    /// doubling chain per row is shared by its terms: 2..8 terms per row go here, 64 and more per instance to `msm_batch`.
+    pub fn ed_lincomb(&self, ps: &[Vec<EdwardsPoint>], ks: &[Vec<Scalar>]) -> Result<Vec<EdwardsPoint>> {
+        assert_eq!(ps.len(), ks.len());
+        let t = ps.first().map_or(1, |p| p.len());
+        let mut fp = Vec::with_capacity(ps.len() * t * 20);
+        let mut fk = Vec::with_capacity(ps.len() * t * 5);
+        for (p, k) in ps.iter().zip(ks) {
+            assert!(p.len() == t && k.len() == t);
+            fp.extend(flat_ed(p));
+            fk.extend(flat_sc(k));
+        }
+        if ps.is_empty() {
+            return Ok(Vec::new());
+        }
+        let mut out = vec![0u64; 20 * ps.len()];
+        check(unsafe { ffi::zc_ed_lincomb(self.ctx, fp.as_ptr(), fk.as_ptr(), t, out.as_mut_ptr(), ps.len()) })?;
+        Ok(unflat_ed(&out))
+    }
+
     // -------------------------------------------------------------- sharded MSM: the exchange step
     /// This device's partial sum, left in device memory (`out_dev`: 160 bytes of HIP memory).
     pub unsafe fn msm_partial(&self, points: *const u64, scalars: *const u64, n: usize, out_dev: *mut u64) -> Result<()> {

@@ -3,6 +3,7 @@
 // lane, grid = ceil(n / 256).  I/O arrays are the reference's own AoS limb layout.
 #pragma once
 #include "zc_curve.hip.h"
+#include "zc_msm_plan.h"      // ZC_BLOCK and the constants the MSM kernels share with the host-side plans
 
 namespace zc {
 
@@ -10,7 +11,6 @@ namespace zc {
 // same, with the register budget capped so that two waves fit on a SIMD
 #define ZC_KERNEL_3W extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
 #define ZC_KERNEL_2W extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-constexpr int ZC_BLOCK = 256;
 
 ZC_DI size_t gid() { return (size_t)blockIdx.x * ZC_BLOCK + threadIdx.x; }
 ZC_DI int wave_max_i32(int v)

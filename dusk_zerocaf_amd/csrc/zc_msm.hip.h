@@ -40,7 +40,8 @@
 #include "zc_quad.hip.h"
 #include "zc_sort.hip.h"
 
-// Compile-time variants of the MSM pipeline (defaults = what was measured best; DESIGN-EXPERIMENTS.md has the numbers):
+// Compile-time variants of the MSM pipeline (defaults = what was measured best; DESIGN-EXPERIMENTS.md has the numbers).
+// Those the host-side plan reads as well -- ZC_MSM_SEG_QUAD, ZC_MSM_LOW_SEG_HALF, ZC_MSM_GROUP_LANES, ZC_MSM_REC_STRIDE -- are in zc_msm_plan.h.
 #ifndef ZC_MSM_TAIL_SIDE
 #define ZC_MSM_TAIL_SIDE 1           // the window groups' chains on the side stream beside the next group's bucket sums (0: in line)
 #endif
@@ -50,20 +51,11 @@
 #ifndef ZC_MSM_FOLD_QUAD
 #define ZC_MSM_FOLD_QUAD 1           // the fold tree with four lanes per addition (0: one lane, 512 points per workgroup)
 #endif
-#ifndef ZC_MSM_SEG_QUAD
-#define ZC_MSM_SEG_QUAD 16384        // four lanes per segment in launches of at most this many segments (twice as many for the lowest of several window groups)
-#endif
-#ifndef ZC_MSM_LOW_SEG_HALF
-#define ZC_MSM_LOW_SEG_HALF 0        // 1: the lowest window group reduces its buckets in segments of half the length.  Round 6, measured and not
-#endif                               // taken: 39 instead of 54 dependent additions, but twice the quads -- k_msm_segments_quad 150 -> 194 us at 2^21 pairs
 #ifndef ZC_MSM_EDGES_QUAD
 #define ZC_MSM_EDGES_QUAD 65536      // four lanes per run in the levels of the segmented reduction with at most this many runs (0: one lane; A/B)
 #endif
 #ifndef ZC_MSM_CARRY_PRESHIFT
 #define ZC_MSM_CARRY_PRESHIFT 1      // the lowest group's Horner rule takes the carry of the groups above already multiplied by 2^(c nw) (0: A/B)
-#endif
-#ifndef ZC_MSM_GROUP_LANES
-#define ZC_MSM_GROUP_LANES 17        // log2 of the lanes a window group's bucket-sum launch keeps busy
 #endif
 #ifndef ZC_MSM_GROUP_WGS
 #define ZC_MSM_GROUP_WGS 3           // workgroups per CU of the bucket-sum launches that run beside a chain (0: no limit)
@@ -71,9 +63,6 @@
 #ifndef ZC_MSM_AFF_LIMBS
 #define ZC_MSM_AFF_LIMBS 1           // affine records hold the kernels' own 29-bit limbs (3 x 9 words = 108 bytes, gathered as 112) instead of three packed
 #endif                               // 256-bit words (96 bytes): the bucket sums skip 3 x 9 limb extractions (64-bit shifts) per addition; same cache line
-#ifndef ZC_MSM_REC_STRIDE
-#define ZC_MSM_REC_STRIDE 128        // stride of the affine records: 128 = one per cache line, 96 = packed (packed 256-bit-word records only)
-#endif
 static_assert(ZC_MSM_REC_STRIDE == 128 || (ZC_MSM_REC_STRIDE == 96 && !ZC_MSM_AFF_LIMBS), "ZC_MSM_REC_STRIDE");
 #ifndef ZC_MSM_ACC_ILP
 #define ZC_MSM_ACC_ILP false   // bucket sums on the column-ordered multiplier: with fixed-length runs every wave has
@@ -83,16 +72,7 @@ static_assert(ZC_MSM_REC_STRIDE == 128 || (ZC_MSM_REC_STRIDE == 96 && !ZC_MSM_AF
 
 namespace zc {
 
-// Buckets per reduction segment (one lane each): short segments keep enough lanes busy when there are few
-// buckets, long ones spend fewer doublings' worth of work on the (first mod 2^(c-1)) * acc products.
-// Measured (2^16 / 2^18 / 2^20 / 2^21 / 2^24 pairs, ms): 8: 1.10 / 1.50 / 2.81 / 4.53 / 24.75,
-// 16: 1.17 / 1.55 / 2.77 / 4.42 / 24.40, 32: 1.30 / 1.68 / 2.93 / 4.56 / 24.05.
-inline int msm_segment_buckets(size_t nbuckets)
-{
-    return nbuckets <= ((size_t)1 << 18) ? 8 : nbuckets >= ((size_t)1 << 21) ? 32 : 16;
-}
-constexpr int MSM_SCALAR_BITS = 261;   // 260-bit limb patterns + the carry of the signed recoding
-constexpr int MSM_MIN_C = 5, MSM_MAX_C = 22;
+// (msm_segment_buckets, MSM_SCALAR_BITS, MSM_MIN_C / MSM_MAX_C, MSM_RAW_WORDS: zc_msm_plan.h)
 
 // c bits of the 260-bit scalar starting at bit `bit` (5 x 52-bit limbs), c <= 32
 ZC_DI u32 scalar_bits(const u64 (&l)[5], int bit, int c)
@@ -349,7 +329,6 @@ void k_msm_prepare_affine(const u64* points, u32* recs, size_t n, int c, u32 rec
 // one-byte flag per bucket (zero-filled per call: 144 times less than the records) says whether the
 // record was written; an unwritten bucket is the identity.  In the edge lists an all-zero record
 // stands for the identity (Z == 0 never occurs for a point).
-constexpr int MSM_RAW_WORDS = 36;
 ZC_DI void pt_store_raw(u32* __restrict__ o, const pt& p)
 {
     uint4* v = reinterpret_cast<uint4*>(o);               // 144-byte records: 16-byte aligned

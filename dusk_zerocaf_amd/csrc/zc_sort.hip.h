@@ -28,27 +28,10 @@
 
 namespace zc {
 
-constexpr int MSM_SORT_PASS_BITS = 9;                          // at most 512 bins per pass (+ 1 in the last)
-constexpr int MSM_SORT_KPT = 16;                               // keys per thread and tile of the scatter kernel: tiles of 4096 keys,
-constexpr int MSM_SORT_KPT_BIG = 32;                           // or of 8192 (two-word records of large batches: a bin's share of a
-                                                               // tile is then a whole 128-byte line even with 512 bins)
+// (MSM_SORT_PASS_BITS, MSM_SORT_KPT(_BIG), SCAN_BLOCK_ELEMS and struct msm_sort_pass: zc_msm_plan.h, shared with the host-side plan)
 constexpr int MSM_SORT_BINS_PAD = 514;                         // >= 513
 constexpr u32 MSM_SORT_NONE = 0xFFFFFFFFu;                     // no key (a key never has all bits set)
 constexpr int MSM_SORT_MATCH_BITS = 7;                         // bin bits matched through the LDS mask table when ranking
-
-struct msm_sort_pass {
-    u32 n;        // keys per window
-    u32 W;        // windows
-    u32 tile;     // keys per tile (256 x keys per thread of the scatter kernel)
-    u32 G;        // tiles per column
-    u32 ncols;    // columns per window = ceil(n / (G * TILE))
-    u32 shift;    // first digit bit of this pass
-    u32 bits;     // digit bits of this pass
-    u32 last;     // 1: the pass that takes the top bits (bin = d >> shift, zero digits -> bin 2^bits)
-    u32 c;        // window width
-    u32 idx_bits; // PACKED records: bits of the point index field
-    u32 w0;       // the table's first window (a sort over a GROUP of windows: W of them from w0 on, positions relative to the group's start)
-};
 
 ZC_DI u32 msm_sort_bins(const msm_sort_pass& p) { return (1u << p.bits) + p.last; }
 ZC_DI u32 msm_sort_bin(const msm_sort_pass& p, u32 key)
@@ -88,7 +71,6 @@ ZC_DI u32 block_exclusive_scan(u32 v, u32* __restrict__ wsum, u32* __restrict__ 
 
 // ---------------------------------------------------------------- flat exclusive scan of a u32 array
 // reduce-then-scan in blocks of 4096 entries; the array is padded (zeros) to a whole number of blocks
-constexpr int SCAN_BLOCK_ELEMS = ZC_BLOCK * 16;
 ZC_KERNEL void k_scan_reduce(const u32* a, u32* sums)
 {
     __shared__ u32 wsum[4];

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +24,7 @@
 #include "zc_msm.hip.h"
 
 using zc::u64;
+using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
 
 namespace {
 
@@ -36,6 +38,17 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
         g_last_error += hipGetErrorString(e);
     }
     return code;
+}
+
+// the same with a formatted message
+__attribute__((format(printf, 2, 3))) int failf(int code, const char* fmt, ...)
+{
+    char msg[160];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    return fail(code, msg);
 }
 
 #define HIP_TRY(expr)                                              \
@@ -64,19 +77,11 @@ struct Tuning {
     bool ristretto_strict = false;   // ZC_RISTRETTO_STRICT=1: config-4 round trip on the reference's formula sequence
     long inv_chunk = 0;              // ZC_INV_CHUNK=c (1..64): elements per lane sharing one inversion
     int jacobi_rounds = -1;          // ZC_JACOBI_ROUNDS=r (0..200): rounds before legendre_symbol falls back to the power
-    int msm_window = 0;              // ZC_MSM_WINDOW=c
-    int msm_affine = -1;             // ZC_MSM_AFFINE=0/1: projective 128-byte records / affine 112-byte records whatever the shard size
-    int msm_groups[4] = {0, 0, 0, 0};   // ZC_MSM_GROUPS="a,b[,c[,d]]": windows per group, top group first ("1" = one group)
-    int msm_ngroups = 0;
+    zc::MsmKnobs msm;                // what the MSM plans read (zc_msm_plan.h): ZC_MSM_WINDOW / _AFFINE / _GROUPS and, in the test-hooks build,
+                                     // ZC_MSM_SORT_PACKED / _SORT_BIG / _SORT_G / _RUN / _RUN_EDGES / _SEG
     // ---- test-hooks build only
-    int msm_sort_packed = -1;        // ZC_MSM_SORT_PACKED=0/1
-    int msm_sort_big = -1;           // ZC_MSM_SORT_BIG=0/1
-    long msm_sort_g = 0;             // ZC_MSM_SORT_G=g (1..64)
-    int msm_run = 0;                 // ZC_MSM_RUN=T (4..4096)
-    int msm_run_edges = 0;           // ZC_MSM_RUN_EDGES=T (4..4096, even)
     int msm_fork = -1;               // ZC_MSM_FORK=0/1
     int msm_affine_chunk = 0;        // ZC_MSM_AFFINE_CHUNK=c (1..64)
-    int msm_seg = 0;                 // ZC_MSM_SEG=s (power of two, 2..256)
     long test_stream_min = 0;        // ZC_TEST_STREAM_MIN_BYTES=b: the 40-byte element ops take their LDS-staged kernels from b bytes per call on
     bool test_ring_poison = false;   // ZC_TEST_RING_POISON: pretend a wave of every windowed-core launch gave up
     unsigned test_ring_spins = 0;    // ZC_TEST_RING_SPINS=b: waves give up after 2^b polls (default 22, about 4 s)
@@ -101,29 +106,29 @@ Tuning tuning_from_env()
     t.ristretto_strict = env_long("ZC_RISTRETTO_STRICT", 0, 1 << 30, 0) != 0;
     t.inv_chunk = env_long("ZC_INV_CHUNK", 1, 64, 0);
     t.jacobi_rounds = (int)env_long("ZC_JACOBI_ROUNDS", 0, 200, -1);
-    t.msm_window = (int)env_long("ZC_MSM_WINDOW", 1, 64, 0);
-    t.msm_affine = (int)env_long("ZC_MSM_AFFINE", 0, 1 << 30, -1);
+    t.msm.window = (int)env_long("ZC_MSM_WINDOW", 1, 64, 0);
+    t.msm.affine = (int)env_long("ZC_MSM_AFFINE", 0, 1 << 30, -1);
     if (const char* e = getenv("ZC_MSM_GROUPS")) {
-        for (const char* q = e; *q && t.msm_ngroups < 4;) {
+        for (const char* q = e; *q && t.msm.ngroups < 4;) {
             char* end = nullptr;
             const long x = strtol(q, &end, 10);
             if (end == q || x < 1 || x > 64) break;
-            t.msm_groups[t.msm_ngroups++] = (int)x;
+            t.msm.groups[t.msm.ngroups++] = (int)x;
             if (*end != ',') break;
             q = end + 1;
         }
     }
 #ifdef ZC_TEST_HOOKS
-    t.msm_sort_packed = (int)env_long("ZC_MSM_SORT_PACKED", 0, 1 << 30, -1);
-    t.msm_sort_big = (int)env_long("ZC_MSM_SORT_BIG", 0, 1 << 30, -1);
-    t.msm_sort_g = env_long("ZC_MSM_SORT_G", 1, 64, 0);
-    t.msm_run = (int)env_long("ZC_MSM_RUN", 4, 4096, 0);
-    t.msm_run_edges = (int)env_long("ZC_MSM_RUN_EDGES", 4, 4096, 0);
+    t.msm.sort_packed = (int)env_long("ZC_MSM_SORT_PACKED", 0, 1 << 30, -1);
+    t.msm.sort_big = (int)env_long("ZC_MSM_SORT_BIG", 0, 1 << 30, -1);
+    t.msm.sort_g = env_long("ZC_MSM_SORT_G", 1, 64, 0);
+    t.msm.run = (int)env_long("ZC_MSM_RUN", 4, 4096, 0);
+    t.msm.run_edges = (int)env_long("ZC_MSM_RUN_EDGES", 4, 4096, 0);
     t.msm_fork = (int)env_long("ZC_MSM_FORK", 0, 1 << 30, -1);
     t.msm_affine_chunk = (int)env_long("ZC_MSM_AFFINE_CHUNK", 1, 64, 0);
     {
         const long f = env_long("ZC_MSM_SEG", 2, 256, 0);
-        if (f && (f & (f - 1)) == 0) t.msm_seg = (int)f;
+        if (f && (f & (f - 1)) == 0) t.msm.seg = (int)f;
     }
     t.test_stream_min = env_long("ZC_TEST_STREAM_MIN_BYTES", 1, 1l << 40, 0);
     t.test_ring_poison = getenv("ZC_TEST_RING_POISON") != nullptr;
@@ -610,8 +615,6 @@ int scalar_mul_bcast(zc_ctx* ctx, const uint64_t* p, const uint64_t (&k)[5], uin
 }
 
 // ---------------------------------------------------------------- MSM device pipeline
-constexpr size_t MSM_BUCKET_MIN_N = 1 << 12;
-
 // pairwise folds until one point is left; returns the buffer holding it
 const u64* fold_all(DevState& D, u64* a, u64* b, size_t cnt)
 {
@@ -625,89 +628,30 @@ const u64* fold_all(DevState& D, u64* a, u64* b, size_t cnt)
     return cur;
 }
 
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T> T* take(size_t count)
-    {
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
+// The device's one MSM workspace (D.msm) as the call's plan lays it out (zc_msm_plan.h: msm_workspace_layout), grown when the
+// call needs more than the device holds; valid until the next MSM on this device.
+struct MsmWorkspace {
+    zc::u32* digits;                      // m window-major digit words
+    uint2* pairs_a;                       // m sorted pairs
+    void* pairs_b;                        // the sort's other buffer: m pairs, m words when the plan is packed, null for one pass
+    zc::u32 *sort_table, *sort_sums;      // two tables of sort.table_words words, the scan's block sums
+    zc::u32 *cached, *buckets;
+    uint8_t* present;
+    zc::u32 *ekeys[2], *erecs[2];         // edge lists of the segmented reduction, ping-pong
+    u64 *seg_out, *fold_b, *out;
 };
-
-// Window width: signed digits put 2^(c-1) buckets in a window; c = log2(n) - 4 keeps about 32
-// points per bucket, where the bucket reduction (~3.7 additions per bucket) stays well below the
-// bucket sums (1 addition per point and window); measured flat within 3 % for c +- 1 up to 2^18 and at 2^21,
-// and for c = 18..21 at 2^24 (tools/quick_bench.py msmsweep).  ZC_MSM_WINDOW=c overrides (tests, tuning; read at context creation like every knob).
-int msm_window_bits(size_t cnt, const Tuning& tune)
+int msm_workspace(DevState& D, const MsmBucketPlan& p, size_t cached_points, size_t out_points, MsmWorkspace* ws, bool sort_only = false)
 {
-    int c = 0;
-    while (((size_t)1 << (c + 1)) <= cnt) c++;
-    c -= 4;
-    if (c == 15 || c == 16) c = 17;                       // 2^19, 2^20 pairs: 16 windows of 17 bits beat 18 of 15 / 17 of 16 (measured -4 %)
-    if (c < zc::MSM_MIN_C) c = zc::MSM_MIN_C;
-    if (c > 18) c = 18;                                   // beyond: no faster (2^24 pairs: c = 18 / 19 / 20: 21.4 / 21.9 / 22.9 ms), bucket memory doubles per step
-    if (tune.msm_window >= zc::MSM_MIN_C && tune.msm_window <= zc::MSM_MAX_C) c = tune.msm_window;
-    return c;
+    const zc::MsmLayout l = zc::msm_workspace_layout(p, cached_points, out_points, sort_only);
+    if (int rc = ensure(&D.msm, &D.msm_bytes, l.total)) return rc;
+    char* const b = (char*)D.msm;
+    *ws = MsmWorkspace{(zc::u32*)(b + l.digits), (uint2*)(b + l.pairs_a), p.sort.passes == 1 ? nullptr : (void*)(b + l.pairs_b),
+                       (zc::u32*)(b + l.sort_table), (zc::u32*)(b + l.sort_sums), (zc::u32*)(b + l.cached), (zc::u32*)(b + l.buckets),
+                       (uint8_t*)(b + l.present), {(zc::u32*)(b + l.ekeys[0]), (zc::u32*)(b + l.ekeys[1])},
+                       {(zc::u32*)(b + l.erecs[0]), (zc::u32*)(b + l.erecs[1])}, (u64*)(b + l.seg_out), (u64*)(b + l.fold_b), (u64*)(b + l.out)};
+    return ZC_OK;
 }
 
-// The key sort of the MSM (zc_sort.hip.h): `passes` stable counting-sort passes over the c - 1 digit bits of
-// every window, at most 9 bits each.  A table column = G tiles of 4096 keys walked by one workgroup of the
-// scatter kernel; G grows with the batch so that every window keeps about 128 columns (2^21 pairs per window:
-// G = 4; 2^24: G = 16), which bounds the table (windows x bins x columns words) at a few MB.
-struct MsmSortPlan {
-    int passes = 0;
-    bool packed = false;                                      // two passes with the one-word intermediate (zc_sort.hip.h):
-                                                              // sign | high digit bits + the zero-digit flag | point index fit 32 bits
-    bool big = false;                                         // tiles of 8192 keys
-    zc::msm_sort_pass pass[4];
-    size_t table_words = 0;                                   // largest table, padded to whole scan blocks
-};
-MsmSortPlan msm_sort_plan(size_t n, int c, int W, const Tuning& tune)
-{
-    MsmSortPlan pl;
-    const int B = c - 1;
-    pl.passes = (B + zc::MSM_SORT_PASS_BITS - 1) / zc::MSM_SORT_PASS_BITS;
-    // two-word records of large batches: tiles of 8192 keys (ZC_MSM_SORT_BIG=0/1 forces the choice)
-    int idx_bits = 1;
-    while (((size_t)1 << idx_bits) < n) idx_bits++;
-    pl.packed = pl.passes == 2 && 1 + (B - (B + 1) / 2) + 1 + idx_bits <= 32 && tune.msm_sort_packed != 0;
-    pl.big = !pl.packed && n >= ((size_t)1 << 22);
-    if (tune.msm_sort_big >= 0) pl.big = !pl.packed && tune.msm_sort_big != 0;
-    const size_t tile = (size_t)zc::ZC_BLOCK * (pl.big ? zc::MSM_SORT_KPT_BIG : zc::MSM_SORT_KPT);
-    const size_t ntiles = (n + tile - 1) / tile;
-    size_t G = ntiles / 128;
-    G = std::max<size_t>(1, std::min<size_t>(16, G));
-    if (tune.msm_sort_g) G = (size_t)tune.msm_sort_g;
-    const size_t ncols = (ntiles + G - 1) / G;
-    int shift = 0;
-    for (int i = 0; i < pl.passes; i++) {
-        const int bits = B / pl.passes + (i < B % pl.passes ? 1 : 0);
-        zc::msm_sort_pass& p = pl.pass[i];
-        p.n = (zc::u32)n;
-        p.W = (zc::u32)W;
-        p.tile = (zc::u32)tile;
-        p.G = (zc::u32)G;
-        p.ncols = (zc::u32)ncols;
-        p.shift = (zc::u32)shift;
-        p.bits = (zc::u32)bits;
-        p.last = i + 1 == pl.passes ? 1u : 0u;
-        p.c = (zc::u32)c;
-        p.idx_bits = pl.packed ? (zc::u32)idx_bits : 0;
-        p.w0 = 0;
-        shift += bits;
-        const size_t words = ((size_t)W * ((size_t)1 << bits) + (p.last ? (size_t)W : 0)) * ncols;
-        pl.table_words = std::max(pl.table_words, (words + zc::SCAN_BLOCK_ELEMS - 1) / zc::SCAN_BLOCK_ELEMS * zc::SCAN_BLOCK_ELEMS);
-    }
-    return pl;
-}
-// table words of one pass over `nw` windows, padded to whole scan blocks
-inline size_t msm_sort_table_words(const zc::msm_sort_pass& p, size_t nw)
-{
-    const size_t words = (nw * ((size_t)1 << p.bits) + (p.last ? nw : 0)) * p.ncols;
-    return (words + zc::SCAN_BLOCK_ELEMS - 1) / zc::SCAN_BLOCK_ELEMS * zc::SCAN_BLOCK_ELEMS;
-}
 // Sorts the windows [w0, w0 + nw) of the window-major digit words on stream `st`: pairs ordered by bucket in buf_a, in the
 // windows' own part of the arrays ([w0 n, (w0 + nw) n): buckets first, the zero digits of these windows behind them).  With
 // w0 = 0, nw = W that is the whole list with every zero digit at its end; a pipeline that takes the windows in groups sorts
@@ -728,8 +672,7 @@ int msm_sort(DevState& D, hipStream_t st, const MsmSortPlan& pl, int w0, int nw,
         p.W = (zc::u32)nw;
         p.w0 = (zc::u32)w0;
         zc::u32* table = tables + (size_t)(i & 1) * table_words;
-        const size_t words = ((size_t)p.W * ((size_t)1 << p.bits) + (p.last ? (size_t)p.W : 0)) * p.ncols;
-        const size_t padded = msm_sort_table_words(p, (size_t)nw);
+        const size_t words = zc::msm_sort_table_rows(p, (size_t)nw), padded = zc::msm_sort_table_words(p, (size_t)nw);
         const unsigned nblk = (unsigned)(padded / zc::SCAN_BLOCK_ELEMS), grid = (unsigned)(p.W * p.ncols);
         if (padded > words) HIP_TRY(hipMemsetAsync(table + words, 0, (padded - words) * sizeof(zc::u32), st));
         hipLaunchKernelGGL(!i ? zc::k_msm_sort_hist : pl.packed ? zc::k_msm_sort_hist_packed : zc::k_msm_sort_hist_pairs, dim3(grid), dim3(zc::ZC_BLOCK), 0, st, in, table, p);
@@ -750,152 +693,33 @@ int msm_sort(DevState& D, hipStream_t st, const MsmSortPlan& pl, int w0, int nw,
     return ZC_OK;
 }
 
-// Affine cached records (7-multiplication bucket additions, 112-byte gathers) from this many points on: the
-// normalisation costs one division-step inversion per lane, which small batches cannot amortise.
-// ZC_MSM_AFFINE=0/1 forces the choice (tests, A/B).
-constexpr size_t MSM_AFFINE_MIN_N = (size_t)1 << 17;
-inline bool msm_affine(size_t cnt, const Tuning& tune)
-{
-    if (tune.msm_affine >= 0) return tune.msm_affine != 0;
-    return cnt >= MSM_AFFINE_MIN_N;
-}
-
-// Everything the pipeline derives from the shard size and the knobs, in one place (also what zc_msm_plan reports).
-struct MsmPlan {
-    bool buckets = false;          // false: below MSM_BUCKET_MIN_N -- n scalar multiplications + pairwise folds
-    int c = 0, W = 0;              // window bits, windows
-    bool affine = false;           // affine records (27 limb words) + 7-multiplication additions (else 128-byte projective, 8)
-    int T = 0, TE = 0;             // run lengths of the segmented reduction: level 0, deeper levels
-    int seg = 0;                   // buckets per reduction segment
-    size_t m = 0, nb = 0, nseg = 0;   // list entries (n W), buckets, segments
-    int rec_bytes = 128;           // stride of the cached records (affine: 96 packed or 128 = one per cache line; projective: 128)
-    int G = 1;                     // window groups, top windows first: gw[g] windows, run length gT[g]
-    int gw[4] = {0, 0, 0, 0}, gT[4] = {0, 0, 0, 0};
-    int gseg[4] = {0, 0, 0, 0};    // buckets per reduction segment, per group (the lowest group's chain is exposed: shorter segments)
-    int bad_groups = 0;            // ZC_MSM_GROUPS was given and adds up to this many windows instead of W: the call fails
-    MsmSortPlan sort;
-};
-// Run length of the bucket-sum kernel for a list of m entries: 128 entries per lane, fewer when the list is short (keep
-// >= 2^17 lanes = two waves per SIMD busy); longer runs leave fewer edges (2 per run) for the deeper levels.
-// Measured (tools/quick_bench.py, ZC_MSM_RUN / ZC_MSM_RUN_EDGES): 2^20 pairs T = 32 / 128 / 256: 2.90 / 2.83 / 3.12 ms;
-// 2^21: 4.67 / 4.48 / 4.52; edge runs of 8 / 16 / 32: 2^21 4.44 / 4.53 / 4.63 ms.  Round 3, 2^24 pairs (2^27.9
-// entries): T = 128 / 256: 21.94 / 21.53 ms -- half the edges for the deeper levels.
-inline int msm_run_length(size_t m, const Tuning& tune, int lanes_log2 = 17)
-{
-    if (tune.msm_run) return tune.msm_run;                // T >= 4: every level shortens the list (2 ceil(len / T) < len)
-    return m >= ((size_t)1 << 27) ? 256 : (int)std::min<size_t>(128, std::max<size_t>(8, m >> lanes_log2));
-}
-MsmPlan msm_plan(size_t cnt, bool points_aligned16, const Tuning& tune)
-{
-    MsmPlan p;
-    if (cnt < MSM_BUCKET_MIN_N) return p;
-    p.buckets = true;
-    p.c = msm_window_bits(cnt, tune);
-    p.W = (zc::MSM_SCALAR_BITS + p.c - 1) / p.c;          // any 260-bit pattern + the recoding carry
-    p.m = cnt * (size_t)p.W;
-    p.nb = (size_t)p.W << (p.c - 1);                      // buckets (digit magnitudes 1 .. 2^(c-1) per window)
-    p.seg = tune.msm_seg ? tune.msm_seg : zc::msm_segment_buckets(p.nb);
-    while (p.seg > (1 << (p.c - 1))) p.seg >>= 1;        // a segment never spans windows (ZC_MSM_SEG beside a narrow ZC_MSM_WINDOW)
-    p.nseg = p.nb / (size_t)p.seg;
-    p.sort = msm_sort_plan(cnt, p.c, p.W, tune);
-    p.affine = msm_affine(cnt, tune) && points_aligned16;  // the normalisation moves the point records with 16-byte loads
-    // affine records: 108 bytes of payload (rounds 3-5: 96) at a 128-byte stride -- one record per cache line.  Packed (96-byte stride) three records
-    // of four straddle two lines: measured (rocprofv3 TCC_EA0_RDREQ of k_msm_runs_affine, profiles/r04_msm_record_stride.md)
-    // 34.6 -> 25.1 read requests per pair at 2^21 pairs, 34.3 -> 27.7 at 2^24; 2^21: 3.50 -> 3.50 ms, 2^22: 6.30 -> 6.13, 2^24: 21.18 -> 20.22.
-    p.rec_bytes = p.affine ? ZC_MSM_REC_STRIDE : 128;
-    p.T = msm_run_length(p.m, tune);
-    p.TE = 8;                                             // deeper levels: short lists, short runs (even: see k_msm_runs_edges)
-    if (tune.msm_run_edges) p.TE = tune.msm_run_edges & ~1;
-    // Window groups (msm_on_device): ZC_MSM_GROUPS="a,b,.." = windows per group, top group first; must add up to W.
-    p.G = 1;
-    p.gw[0] = p.W;
-    {
-        int sum = 0;
-        for (int g = 0; g < tune.msm_ngroups; g++) sum += tune.msm_groups[g];
-        if (tune.msm_ngroups >= 2 && sum == p.W) {
-            p.G = tune.msm_ngroups;
-            for (int g = 0; g < p.G; g++) p.gw[g] = tune.msm_groups[g];
-        } else if (tune.msm_ngroups >= 2) {
-            p.bad_groups = sum;                           // fail closed: a split for another window count is not silently replaced by one group
-        } else if (tune.msm_ngroups == 0 && p.W >= 8 && cnt >= ((size_t)1 << 21) && cnt < ((size_t)1 << 22)) {
-            // default for config-5-sized shards (2^21 pairs: 16 windows as 9 + 4 + 3): three groups, the lowest (exposed) one the
-            // smallest.  Measured on one box, 2^21 pairs (tools/msm_groups_sweep.py): one group 3.68 ms, 13+3 3.50, 12+4 3.51,
-            // 10+6 3.74, 7+6+3 3.55, 8+5+3 3.55, 9+4+3 3.44, 6+6+4 3.50, four groups 3.8 - 4.1.  Below 2^21 and from 2^22 on
-            // the groups gain nothing (2^20: 2.39 -> 2.59 ms; 2^22: 6.27 -> 6.24; 2^24: 21.2 -> 21.6): one group.
-            p.G = 3;
-            p.gw[2] = std::max(1, (3 * p.W + 8) / 16);
-            p.gw[1] = std::max(1, (4 * p.W + 8) / 16);
-            p.gw[0] = p.W - p.gw[1] - p.gw[2];
-        }
-    }
-    // a group's launch keeps 2^17 lanes busy like the whole list (ZC_MSM_GROUP_LANES=16 / 17 / 18 / 19 at 2^21 pairs in three groups:
-    // 3.71 / 3.48 / 3.61 / 4.30 ms: shorter runs cut more buckets, and every cut is an edge for the levels behind)
-    for (int g = 0; g < p.G; g++)
-        p.gT[g] = p.G == 1 ? p.T : msm_run_length(cnt * (size_t)p.gw[g], tune, ZC_MSM_GROUP_LANES);
-    // Segment length per group.  (ZC_MSM_LOW_SEG_HALF: half the length for the lowest group, whose chain is on the call's critical
-    // path -- 39 instead of 54 dependent additions; measured in round 6 and not taken, the segments are not pure latency.)
-    for (int g = 0; g < p.G; g++) {
-        p.gseg[g] = p.seg;
-        const size_t nsegg2 = 2 * (size_t)p.gw[g] * (((size_t)1 << (p.c - 1)) / (size_t)p.seg);
-        if (ZC_MSM_LOW_SEG_HALF && p.G > 1 && g == p.G - 1 && !tune.msm_seg && p.seg >= 4 && nsegg2 <= 2 * (size_t)ZC_MSM_SEG_QUAD) p.gseg[g] = p.seg / 2;
-    }
-    p.nseg = 0;
-    for (int g = 0; g < p.G; g++) p.nseg += (size_t)p.gw[g] * (((size_t)1 << (p.c - 1)) / (size_t)p.gseg[g]);
-    return p;
-}
-
-// ---------------------------------------------------------------- fixed-base MSM plan (zc_msm_bases_create / zc_msm_fixed)
-// Window width of a table of n bases: per scalar vector the bucket sums cost n W additions and the reduction about 3.7 per
-// bucket (the figure behind msm_window_bits), 2^(c-1) buckets: c minimises n ceil(261 / c) + 3.7 2^(c-1).  There is no
-// doubling chain to hide, and c is fixed when the table is built.
-int msm_fixed_window_bits(size_t n)
-{
-    int best = zc::MSM_MIN_C;
-    double best_cost = 0;
-    for (int c = zc::MSM_MIN_C; c <= zc::MSM_MAX_C; c++) {
-        const double cost = (double)n * (double)((zc::MSM_SCALAR_BITS + c - 1) / c) + 3.7 * (double)((size_t)1 << (c - 1));
-        if (c == zc::MSM_MIN_C || cost < best_cost) best = c, best_cost = cost;
-    }
-    return best;
-}
-// One window group (G = 1) whose "windows" are the batch's scalar vectors: each is a sort window of n W entries.
-struct MsmFixedPlan {
-    int c = 0, W = 0;
-    size_t m = 0, nb = 0;          // list entries (batch n W), buckets (batch 2^(c-1))
-    int T = 0, TE = 8, seg = 0;    // run lengths (level 0, deeper levels), buckets per reduction segment
-    size_t nseg = 0, nl0 = 0;      // segments, level-0 lanes
-    MsmSortPlan sort;
-};
-MsmFixedPlan msm_fixed_plan(size_t n, int c, size_t batch, const Tuning& tune)
-{
-    MsmFixedPlan p;
-    p.c = c;
-    p.W = (zc::MSM_SCALAR_BITS + c - 1) / c;
-    p.m = batch * n * (size_t)p.W;
-    p.nb = batch << (c - 1);
-    p.sort = msm_sort_plan(n * (size_t)p.W, c, (int)std::min<size_t>(batch, 0x7FFFFFFF), tune);
-    p.T = msm_run_length(p.m, tune);
-    if (tune.msm_run_edges) p.TE = tune.msm_run_edges & ~1;
-    p.seg = tune.msm_seg ? tune.msm_seg : zc::msm_segment_buckets(p.nb);
-    while (p.seg > (1 << (c - 1))) p.seg >>= 1;           // a segment never spans windows
-    p.nseg = p.nb / (size_t)p.seg;
-    p.nl0 = (p.m + (size_t)p.T - 1) / (size_t)p.T;
-    return p;
-}
-// window_bits 0 / 5..22 and the index limits of a table of n bases, checked before anything is allocated
+// window_bits 0 / 5..22 and the index limit of a table of n bases, checked before anything is allocated
 int msm_fixed_check(size_t n, int window_bits, int* c_out, int* W_out, const char* who)
 {
-    char msg[160];
-    if (n == 0) return snprintf(msg, sizeof msg, "%s: no bases", who), fail(ZC_ERR_BAD_ARG, msg);
+    if (n == 0) return failf(ZC_ERR_BAD_ARG, "%s: no bases", who);
     if (window_bits != 0 && (window_bits < zc::MSM_MIN_C || window_bits > zc::MSM_MAX_C))
-        return snprintf(msg, sizeof msg, "%s: window_bits %d outside 0 or %d..%d", who, window_bits, zc::MSM_MIN_C, zc::MSM_MAX_C), fail(ZC_ERR_BAD_ARG, msg);
-    const int c = window_bits ? window_bits : msm_fixed_window_bits(n);
-    const int W = (zc::MSM_SCALAR_BITS + c - 1) / c;
-    if (n >= ((size_t)1 << 31) / (size_t)W + 1 || n * (size_t)W >= ((size_t)1 << 31))
-        return snprintf(msg, sizeof msg, "%s: %zu bases x %d windows do not fit 31-bit record indices", who, n, W), fail(ZC_ERR_BAD_ARG, msg);
+        return failf(ZC_ERR_BAD_ARG, "%s: window_bits %d outside 0 or %d..%d", who, window_bits, zc::MSM_MIN_C, zc::MSM_MAX_C);
+    const int c = window_bits ? window_bits : zc::msm_fixed_window_bits(n);
+    const int W = zc::msm_windows(c);
+    if (zc::msm_index_limit(zc::msm_sat_mul(n, (size_t)W), 0, 0))
+        return failf(ZC_ERR_BAD_ARG, "%s: %zu bases x %d windows do not fit 31-bit record indices", who, n, W);
     *c_out = c;
     *W_out = W;
     return ZC_OK;
+}
+// The index limits of a batch, checked before anything is allocated: record indices batch n < 2^31, pair indices
+// batch n W < 2^32, bucket keys batch W 2^(c-1) < 2^32 (c, W: the bucket regime's, whichever regime runs).
+int msm_batch_check(size_t n, size_t batch, const Tuning& tune, const char* who)
+{
+    if (n == 0 || batch == 0) return ZC_OK;
+    const int c = zc::msm_batch_window_bits(n, tune.msm);
+    const size_t W = (size_t)zc::msm_windows(c), cnt = zc::msm_sat_mul(n, batch);
+    switch (zc::msm_index_limit(cnt, zc::msm_sat_mul(cnt, W), zc::msm_sat_mul(zc::msm_sat_mul(batch, W), (size_t)1 << (c - 1)))) {
+    case zc::MSM_LIMIT_RECORDS: return failf(ZC_ERR_BAD_ARG, "%s: %zu instances x %zu pairs do not fit 31-bit record indices", who, batch, n);
+    case zc::MSM_LIMIT_PAIRS: return failf(ZC_ERR_BAD_ARG, "%s: %zu instances x %zu pairs x %zu windows do not fit 32-bit pair indices", who, batch, n, W);
+    case zc::MSM_LIMIT_KEYS: return failf(ZC_ERR_BAD_ARG, "%s: %zu instances x %zu windows x 2^%d buckets do not fit 32-bit bucket keys", who, batch, W, c - 1);
+    default: return ZC_OK;
+    }
 }
 
 // The affine normalisation of cnt points (16-byte aligned) into records of rec_words words, on stream `st`.
@@ -910,8 +734,8 @@ void msm_prepare_affine(hipStream_t st, const u64* dP, zc::u32* recs, size_t cnt
     hipLaunchKernelGGL(zc::k_msm_prepare_affine, dim3((unsigned)((lanes + zc::MSM_PREP_BLOCK - 1) / zc::MSM_PREP_BLOCK)), dim3(zc::MSM_PREP_BLOCK), 0, st, dP, recs, cnt, ac, rec_words);
 }
 
-// The buffers of the bucket sums and their reduction: the lower half of the bucket method, shared by zc_msm (msm_on_device)
-// and zc_msm_fixed.
+// The buffers of the bucket sums and their reduction: the lower half of the bucket method, shared by zc_msm (msm_on_device),
+// zc_msm_batch and zc_msm_fixed.
 struct MsmReduceBufs {
     const uint2* sorted;                  // the key sort's pairs (bucket key, record index | sign << 31)
     const zc::u32* recs;                  // the cached records the pairs name
@@ -924,14 +748,43 @@ struct MsmReduceBufs {
     zc::u32* erecs[2];
     int c, TE;                            // window bits, run length of the deeper levels
 };
+MsmReduceBufs msm_reduce_bufs(const MsmBucketPlan& p, const MsmWorkspace& ws, const zc::u32* recs)
+{
+    return MsmReduceBufs{ws.pairs_a, recs, (zc::u32)(p.rec_bytes / 4), p.affine, p.m, p.nb, ws.buckets, ws.present,
+                         {ws.ekeys[0], ws.ekeys[1]}, {ws.erecs[0], ws.erecs[1]}, p.c, p.TE};
+}
+// One launch sequence of msm_reduce_windows.  The defaults are a flat pipeline's, which names its windows, T, nl0 and the
+// segments only: the whole list, the caller's stream, nothing beside it.
+struct MsmReduceArgs {
+    int w0 = 0, nw = 0, T = 0;            // the windows [w0, w0 + nw); run length of their level-0 bucket sums
+    size_t nl0 = 0, slot0 = 0;            // the lanes of those: [slot0, slot0 + nl0) of the edge arrays
+    const zc::u32 *range_lo = nullptr, *range_end = nullptr;   // the list part [*range_lo, *range_end) (device words); null: the whole list
+    size_t pad = 0;                       // dynamic LDS that pads the bucket-sum workgroups
+    hipStream_t st = nullptr;             // stream of everything behind the bucket sums; null: D.s()
+    hipEvent_t go = nullptr;              // recorded behind the bucket sums when `st` is another stream
+    int seg = 0;                          // buckets per segment
+    size_t nsegg = 0, quad_max = ZC_MSM_SEG_QUAD;   // segments of these windows; four lanes per segment up to this many of them
+    u64 *seg_out = nullptr, *fold_b = nullptr;   // the segment sums and the folds' other buffer: nsegg points each
+};
+MsmReduceArgs msm_reduce_flat(const MsmBucketPlan& p, const MsmWorkspace& ws)
+{
+    MsmReduceArgs a;
+    a.nw = (int)p.nw, a.T = p.T, a.nl0 = p.nl0;
+    a.seg = p.seg, a.nsegg = p.nseg, a.seg_out = ws.seg_out, a.fold_b = ws.fold_b;
+    return a;
+}
 // The windows [w0, w0 + nw): the level-0 bucket sums on D.s() (lanes [slot0, slot0 + nl0) of the edge arrays, over the list part
 // [*range_lo, *range_end) or, with null range pointers, the whole list), then on `st` -- behind the event `go`, recorded here, when
 // that is another stream -- the deeper levels of the segmented reduction, the segment sums (nsegg segments of `seg` buckets, four
 // lanes per segment up to quad_max of them) and the folds down to one point per window.  *sums: the nw window sums (seg_out or fold_b).
-int msm_reduce_windows(DevState& D, const MsmReduceBufs& rb, int w0, int nw, int T, size_t nl0, size_t slot0, const zc::u32* range_lo,
-                       const zc::u32* range_end, size_t pad, hipStream_t st, hipEvent_t go, int seg, size_t nsegg, size_t quad_max, u64* seg_out,
-                       u64* fold_b, u64** sums)
+int msm_reduce_windows(DevState& D, const MsmReduceBufs& rb, const MsmReduceArgs& a, u64** sums)
 {
+    const int w0 = a.w0, nw = a.nw, T = a.T, seg = a.seg;
+    const size_t nl0 = a.nl0, slot0 = a.slot0, pad = a.pad, nsegg = a.nsegg, quad_max = a.quad_max;
+    const zc::u32 *range_lo = a.range_lo, *range_end = a.range_end;
+    hipStream_t st = a.st ? a.st : D.s();
+    hipEvent_t go = a.go;
+    u64 *seg_out = a.seg_out, *fold_b = a.fold_b;
     const int c = rb.c, TE = rb.TE;
     const size_t m = rb.m, nb = rb.nb;
     zc::u32* const buckets = rb.buckets;
@@ -1005,7 +858,7 @@ int msm_reduce_windows(DevState& D, const MsmReduceBufs& rb, int w0, int nw, int
 // *result points at the 160-byte sum in D's memory (valid until the next MSM on this device).
 int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u64** result)
 {
-    if (cnt < MSM_BUCKET_MIN_N) {
+    if (cnt < zc::MSM_BUCKET_MIN_N) {
         // small shard: n scalar-muls, then pairwise folds
         int rc = ensure(&D.tmp[0], &D.tmp_bytes[0], cnt * 160);
         if (rc) return rc;
@@ -1016,19 +869,14 @@ int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u
         HIP_TRY(hipGetLastError());
         return ZC_OK;
     }
-    if (cnt > 0x7FFFFFFFull) return fail(ZC_ERR_BAD_ARG, "zc_msm: shard too large for 31-bit point indices");
+    if (zc::msm_index_limit(cnt, 0, 0)) return fail(ZC_ERR_BAD_ARG, "zc_msm: shard too large for 31-bit point indices");
     const Tuning& tune = D.tune;
-    const MsmPlan mp = msm_plan(cnt, aligned16(dP), tune);
-    if (mp.bad_groups) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "zc_msm: ZC_MSM_GROUPS adds up to %d windows, a shard of %zu pairs has %d (%d-bit windows)", mp.bad_groups, cnt, mp.W, mp.c);
-        return fail(ZC_ERR_BAD_ARG, msg);
-    }
-    const int c = mp.c, W = mp.W, TE = mp.TE;
-    const size_t m = mp.m, nb = mp.nb, nseg = mp.nseg;
-    if (m > 0xFFFFFFFFull) return fail(ZC_ERR_BAD_ARG, "zc_msm: shard too large for 32-bit pair indices");
+    const MsmPlan mp = msm_plan(cnt, aligned16(dP), tune.msm);
+    if (mp.bad_groups)
+        return failf(ZC_ERR_BAD_ARG, "zc_msm: ZC_MSM_GROUPS adds up to %d windows, a shard of %zu pairs has %d (%d-bit windows)", mp.bad_groups, cnt, mp.W, mp.c);
+    const int c = mp.c, W = mp.W;
+    if (zc::msm_index_limit(0, mp.m, 0)) return fail(ZC_ERR_BAD_ARG, "zc_msm: shard too large for 32-bit pair indices");
     const MsmSortPlan& plan = mp.sort;
-    const bool affine = mp.affine;
     // ---- window groups.  Everything behind the bucket sums -- the deeper levels of the segmented reduction, the bucket
     // reduction, Horner's rule -- is a chain of dependent point operations on few waves: a third of a 2^21 shard during
     // which the chip idles.  The sorted list is ordered by window, so the bucket-sum kernel is launched over the windows
@@ -1043,121 +891,93 @@ int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u
     // 2.2 - 3.3 ms instead of 1.8 -- and at 128 entries per run the launch is a single round of resident workgroups
     // anyway, so its groups all end together.)
     const int G = mp.G;
-    struct Group {
-        int w0 = 0, nw = 0, T = 0;
-        size_t nl0 = 0, slot0 = 0;                         // level-0 lanes (upper bound: the list part's length is known on the device only), first lane in the edge arrays
-        hipStream_t st = nullptr;
-    } grp[4];
-    size_t lanes_total = 0;
-    {
-        int top = W;
-        for (int g = 0; g < G; g++) {
-            grp[g].nw = mp.gw[g];
-            top -= mp.gw[g];
-            grp[g].w0 = top;
-            grp[g].T = mp.gT[g];
-            grp[g].nl0 = (cnt * (size_t)grp[g].nw + grp[g].T - 1) / grp[g].T;
-            grp[g].slot0 = lanes_total;
-            lanes_total += grp[g].nl0;
-            grp[g].st = g == G - 1 ? D.s() : D.grp;          // ONE side stream: streams of one priority share a hardware queue here anyway
-        }
+    // one sort for all windows (a sort per window group under the bucket sums of the group above was built and measured in
+    // round 5 -- not taken; the patch: tools/debug/probes/msm_sort_per_group.patch)
+    MsmWorkspace ws;
+    if (int rc = msm_workspace(D, mp, cnt, (size_t)(G + 1), &ws)) return rc;
+    u64* const grp_out = ws.out;                            // Horner's rule after every group; the lowest group's is the result
+    // the point normalisation (an inversion-heavy, half compute-bound pass) runs on a second stream beside the key
+    // sort (latency- and bandwidth-bound): they share no buffer, and the bucket sums wait for both.  Measured, 2^21 pairs:
+    // 3.89 -> 3.80 ms (the sort's kernels slow down beside it, the pair still ends 60-90 us earlier); at 2^24 both sides are
+    // bandwidth-bound for milliseconds and the pair ends no earlier (21.5 vs 21.7 ms), so large shards stay in line.
+    // ZC_MSM_FORK=0/1 forces the choice.
+    const bool fork = tune.msm_fork >= 0 ? tune.msm_fork != 0 : cnt < ((size_t)1 << 23);
+    hipStream_t ps = D.s();
+    if (fork && D.aux) {
+        HIP_TRY(hipEventRecord(D.ev_fork, D.s()));
+        HIP_TRY(hipStreamWaitEvent(D.aux, D.ev_fork, 0));
+        ps = D.aux;
     }
-    size_t seg_off[5] = {0, 0, 0, 0, 0};                        // group g's part of the segment arrays (segments per window: a power of two per group)
-    for (int g = 0; g < G; g++) seg_off[g + 1] = seg_off[g] + (size_t)grp[g].nw * (((size_t)1 << (c - 1)) / (size_t)mp.gseg[g]);
-    const zc::u32 rec_words = affine ? (zc::u32)(mp.rec_bytes / 4) : 32u;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv{pass ? (char*)D.msm : nullptr};
-        zc::u32* digits = cv.take<zc::u32>(m);
-        uint2* pairs_a = cv.take<uint2>(m);
-        void* pairs_b = plan.passes == 1 ? nullptr : plan.packed ? (void*)cv.take<zc::u32>(m) : (void*)cv.take<uint2>(m);
-        // one sort for all windows (a sort per window group under the bucket sums of the group above was built and measured in
-        // round 5 -- not taken; the patch: tools/debug/probes/msm_sort_per_group.patch)
-        zc::u32* sort_table = cv.take<zc::u32>(2 * plan.table_words);
-        zc::u32* sort_sums = cv.take<zc::u32>(plan.table_words / zc::SCAN_BLOCK_ELEMS + 1);
-        zc::u32* cached = cv.take<zc::u32>(cnt * 32);
-        zc::u32* buckets = cv.take<zc::u32>(nb * zc::MSM_RAW_WORDS);
-        uint8_t* present = cv.take<uint8_t>(nb);
-        zc::u32* ekeys[2] = {cv.take<zc::u32>(2 * lanes_total), cv.take<zc::u32>(2 * lanes_total)};       // edge lists, ping-pong
-        zc::u32* erecs[2] = {cv.take<zc::u32>(2 * lanes_total * zc::MSM_RAW_WORDS), cv.take<zc::u32>(2 * lanes_total * zc::MSM_RAW_WORDS)};
-        u64* seg_out = cv.take<u64>(nseg * 20);
-        u64* fold_b = cv.take<u64>(nseg * 20);
-        u64* grp_out = cv.take<u64>((size_t)(G + 1) * 20);  // Horner's rule after every group; the lowest group's is the result
-        if (!pass) {
-            int rc = ensure(&D.msm, &D.msm_bytes, cv.off);
-            if (rc) return rc;
-            continue;
-        }
-        // the point normalisation (an inversion-heavy, half compute-bound pass) runs on a second stream beside the key
-        // sort (latency- and bandwidth-bound): they share no buffer, and the bucket sums wait for both.  Measured, 2^21 pairs:
-        // 3.89 -> 3.80 ms (the sort's kernels slow down beside it, the pair still ends 60-90 us earlier); at 2^24 both sides are
-        // bandwidth-bound for milliseconds and the pair ends no earlier (21.5 vs 21.7 ms), so large shards stay in line.
-        // ZC_MSM_FORK=0/1 forces the choice.
-        const bool fork = tune.msm_fork >= 0 ? tune.msm_fork != 0 : cnt < ((size_t)1 << 23);
-        hipStream_t ps = D.s();
-        if (fork && D.aux) {
-            HIP_TRY(hipEventRecord(D.ev_fork, D.s()));
-            HIP_TRY(hipStreamWaitEvent(D.aux, D.ev_fork, 0));
-            ps = D.aux;
-        }
-        if (affine) {
-            msm_prepare_affine(ps, dP, cached, cnt, tune, rec_words);
-        } else {
-            hipLaunchKernelGGL(aligned16(dP) ? zc::k_msm_prepare : zc::k_msm_prepare_lane, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, ps, dP, cached, cnt);
-        }
-        if (ps != D.s()) HIP_TRY(hipEventRecord(D.ev_join, ps));
-        hipLaunchKernelGGL(zc::k_msm_digits, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, digits, cnt, c, W);
-        const uint2* sorted = pairs_a;
-        // The key sort
-        HIP_TRY(hipMemsetAsync(present, 0, nb, D.s()));       // one flag per bucket: record written (else: empty = identity)
-        if (int rc = msm_sort(D, D.s(), plan, 0, W, digits, pairs_a, pairs_b, sort_table, plan.table_words, sort_sums)) return rc;
-        if (ps != D.s()) HIP_TRY(hipStreamWaitEvent(D.s(), D.ev_join, 0));
-        // where window w's part of the sorted list starts: the last pass's scanned table at (window w, bin 0, column 0); the row
-        // behind the last window is the zero digits' = the end of the buckets (zc_sort.hip.h: msm_sort_slot).
-        const zc::msm_sort_pass& lastp = plan.pass[plan.passes - 1];
-        auto window_start = [&](int w) {
-            const zc::u32* last_table = sort_table + (size_t)((plan.passes - 1) & 1) * plan.table_words;
-            return last_table + ((size_t)w << lastp.bits) * lastp.ncols;
-        };
-        const MsmReduceBufs rb{sorted, cached, rec_words, affine, m, nb, buckets, present, {ekeys[0], ekeys[1]}, {erecs[0], erecs[1]}, c, TE};
-        for (int g = 0; g < G; g++) {
-            Group& gr = grp[g];
-            // A launch that runs beside the chain of the group above it leaves that chain room: its workgroups are padded with
-            // dynamic LDS so that only `wgs` of them fit a CU (three: one wave slot per SIMD, 200 VGPRs and 39 KB of LDS stay free;
-            // a chain kernel that finds every slot taken waits for a bucket-sum workgroup to retire).
-            size_t pad = 0;
-            if (g > 0) {
-                const long wgs = ZC_MSM_GROUP_WGS;
-                const size_t own = (affine ? zc::MSM_AFF_PIECES : 8) * 16 * (size_t)zc::MSM_RUN_BLOCK;       // the kernel's static staging area
-                if (wgs > 0 && (size_t)(wgs + 1) * own <= 163840) {
-                    const size_t per = 163840 / (size_t)(wgs + 1) + 512;                     // wgs + 1 of these do not fit 160 KB
-                    pad = per > own ? std::min<size_t>(per - own, 65536 - own) : 0;
-                }
+    if (mp.affine) {
+        msm_prepare_affine(ps, dP, ws.cached, cnt, tune, (zc::u32)(mp.rec_bytes / 4));
+    } else {
+        hipLaunchKernelGGL(aligned16(dP) ? zc::k_msm_prepare : zc::k_msm_prepare_lane, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, ps, dP, ws.cached, cnt);
+    }
+    if (ps != D.s()) HIP_TRY(hipEventRecord(D.ev_join, ps));
+    hipLaunchKernelGGL(zc::k_msm_digits, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, ws.digits, cnt, c, W);
+    // The key sort
+    HIP_TRY(hipMemsetAsync(ws.present, 0, mp.nb, D.s()));     // one flag per bucket: record written (else: empty = identity)
+    if (int rc = msm_sort(D, D.s(), plan, 0, W, ws.digits, ws.pairs_a, ws.pairs_b, ws.sort_table, plan.table_words, ws.sort_sums)) return rc;
+    if (ps != D.s()) HIP_TRY(hipStreamWaitEvent(D.s(), D.ev_join, 0));
+    // where window w's part of the sorted list starts: the last pass's scanned table at (window w, bin 0, column 0); the row
+    // behind the last window is the zero digits' = the end of the buckets (zc_sort.hip.h: msm_sort_slot).
+    const zc::msm_sort_pass& lastp = plan.pass[plan.passes - 1];
+    auto window_start = [&](int w) {
+        const zc::u32* last_table = ws.sort_table + (size_t)((plan.passes - 1) & 1) * plan.table_words;
+        return last_table + ((size_t)w << lastp.bits) * lastp.ncols;
+    };
+    const MsmReduceBufs rb = msm_reduce_bufs(mp, ws, ws.cached);
+    int top = W;                                            // group g's windows: the gw[g] below `top`
+    size_t slot0 = 0, seg0 = 0;                             // its first level-0 lane in the edge arrays, its first segment in the segment arrays
+    for (int g = 0; g < G; g++) {
+        MsmReduceArgs ra;
+        ra.nw = mp.gw[g];
+        ra.w0 = top -= ra.nw;
+        ra.T = mp.gT[g];
+        ra.nl0 = (cnt * (size_t)ra.nw + ra.T - 1) / ra.T;     // an upper bound: the list part's length is known on the device only
+        ra.slot0 = slot0;
+        if (G > 1) ra.range_lo = window_start(ra.w0), ra.range_end = window_start(ra.w0 + ra.nw);
+        // A launch that runs beside the chain of the group above it leaves that chain room: its workgroups are padded with
+        // dynamic LDS so that only `wgs` of them fit a CU (three: one wave slot per SIMD, 200 VGPRs and 39 KB of LDS stay free;
+        // a chain kernel that finds every slot taken waits for a bucket-sum workgroup to retire).
+        if (g > 0) {
+            const long wgs = ZC_MSM_GROUP_WGS;
+            const size_t own = (mp.affine ? zc::MSM_AFF_PIECES : 8) * 16 * (size_t)zc::MSM_RUN_BLOCK;       // the kernel's static staging area
+            if (wgs > 0 && (size_t)(wgs + 1) * own <= 163840) {
+                const size_t per = 163840 / (size_t)(wgs + 1) + 512;                     // wgs + 1 of these do not fit 160 KB
+                ra.pad = per > own ? std::min<size_t>(per - own, 65536 - own) : 0;
             }
-            hipStream_t st = ZC_MSM_TAIL_SIDE ? gr.st : D.s();
-            // few segments (the lowest group, small shards): four lanes per segment, three multiplication latencies per addition
-            const size_t quad_max = (size_t)ZC_MSM_SEG_QUAD * (G > 1 && g == G - 1 ? 2 : 1);     // (the exposed chain: lanes for latency)
-            u64* cur = nullptr;
-            if (int rc = msm_reduce_windows(D, rb, gr.w0, gr.nw, gr.T, gr.nl0, gr.slot0, G == 1 ? (const zc::u32*)nullptr : window_start(gr.w0),
-                                            G == 1 ? (const zc::u32*)nullptr : window_start(gr.w0 + gr.nw), pad, st, D.ev_grp_go[g], mp.gseg[g],
-                                            seg_off[g + 1] - seg_off[g], quad_max, seg_out + 20 * seg_off[g], fold_b + 20 * seg_off[g], &cur))
-                return rc;
-            // Horner's rule, top window first across the groups: this group continues from the result of the group above it
-            // (same stream, or -- the lowest group -- behind that stream's event)
-            if (g == G - 1 && G > 1 && ZC_MSM_TAIL_SIDE) HIP_TRY(hipStreamWaitEvent(st, D.ev_grp_done[G - 2], 0));
-            // The lowest group's stretch of the rule is on the call's critical path: it takes the result of the groups above ALREADY
-            // multiplied by 2^(c nw) -- k_msm_shift runs behind the second-lowest group's stretch on the side stream, beside the
-            // lowest group's bucket sums (slot G of grp_out) -- and adds it last.
-            const bool preshift = ZC_MSM_CARRY_PRESHIFT && G > 1 && ZC_MSM_TAIL_SIDE;
-            const bool lowest = g == G - 1;
-            const u64* carry = g == 0 ? nullptr : (lowest && preshift) ? grp_out + 20 * (size_t)G : grp_out + 20 * (size_t)(g - 1);
-            hipLaunchKernelGGL(zc::k_msm_window_combine, dim3(1), dim3(64), 0, st, (const u64*)cur, grp_out + 20 * (size_t)g, gr.nw, c, carry, lowest && preshift ? 1 : 0);
-            if (preshift && g == G - 2)
-                hipLaunchKernelGGL(zc::k_msm_shift, dim3(1), dim3(64), 0, st, (const u64*)(grp_out + 20 * (size_t)g), grp_out + 20 * (size_t)G, c * grp[G - 1].nw);
-            if (st != D.s()) HIP_TRY(hipEventRecord(D.ev_grp_done[g], st));
         }
-        *result = grp_out + 20 * (size_t)(G - 1);
-        HIP_TRY(hipGetLastError());
+        // the chains of the upper groups on ONE side stream: streams of one priority share a hardware queue here anyway
+        hipStream_t st = ZC_MSM_TAIL_SIDE && g < G - 1 ? D.grp : D.s();
+        ra.st = st;
+        ra.go = D.ev_grp_go[g];
+        ra.seg = mp.gseg[g];
+        ra.nsegg = (size_t)ra.nw * (((size_t)1 << (c - 1)) / (size_t)ra.seg);      // segments per window: a power of two per group
+        // few segments (the lowest group, small shards): four lanes per segment, three multiplication latencies per addition
+        ra.quad_max = (size_t)ZC_MSM_SEG_QUAD * (G > 1 && g == G - 1 ? 2 : 1);     // (the exposed chain: lanes for latency)
+        ra.seg_out = ws.seg_out + 20 * seg0;
+        ra.fold_b = ws.fold_b + 20 * seg0;
+        slot0 += ra.nl0;
+        seg0 += ra.nsegg;
+        u64* cur = nullptr;
+        if (int rc = msm_reduce_windows(D, rb, ra, &cur)) return rc;
+        // Horner's rule, top window first across the groups: this group continues from the result of the group above it
+        // (same stream, or -- the lowest group -- behind that stream's event)
+        if (g == G - 1 && G > 1 && ZC_MSM_TAIL_SIDE) HIP_TRY(hipStreamWaitEvent(st, D.ev_grp_done[G - 2], 0));
+        // The lowest group's stretch of the rule is on the call's critical path: it takes the result of the groups above ALREADY
+        // multiplied by 2^(c nw) -- k_msm_shift runs behind the second-lowest group's stretch on the side stream, beside the
+        // lowest group's bucket sums (slot G of grp_out) -- and adds it last.
+        const bool preshift = ZC_MSM_CARRY_PRESHIFT && G > 1 && ZC_MSM_TAIL_SIDE;
+        const bool lowest = g == G - 1;
+        const u64* carry = g == 0 ? nullptr : (lowest && preshift) ? grp_out + 20 * (size_t)G : grp_out + 20 * (size_t)(g - 1);
+        hipLaunchKernelGGL(zc::k_msm_window_combine, dim3(1), dim3(64), 0, st, (const u64*)cur, grp_out + 20 * (size_t)g, ra.nw, c, carry, lowest && preshift ? 1 : 0);
+        if (preshift && g == G - 2)
+            hipLaunchKernelGGL(zc::k_msm_shift, dim3(1), dim3(64), 0, st, (const u64*)(grp_out + 20 * (size_t)g), grp_out + 20 * (size_t)G, c * mp.gw[G - 1]);
+        if (st != D.s()) HIP_TRY(hipEventRecord(D.ev_grp_done[g], st));
     }
+    *result = grp_out + 20 * (size_t)(G - 1);
+    HIP_TRY(hipGetLastError());
     return ZC_OK;
 }
 
@@ -1208,168 +1028,91 @@ DevState* dev_state_of(zc_ctx* ctx, int device)
     return nullptr;
 }
 
+// Where the two input arrays of an MSM live: *owner = the device slot of the context that holds both, null = host memory.
+// `who` prefixes the messages ("" or "zc_...: ").
+int msm_inputs_owner(zc_ctx* ctx, const void* points, const void* scalars, const char* who, DevState** owner)
+{
+    Residency rp, rk;
+    int dp = -1, dk = -1;
+    residency_of(points, &rp, &dp);
+    residency_of(scalars, &rk, &dk);
+    if (rp != rk || (rp == RES_DEVICE && dp != dk)) return failf(ZC_ERR_MIXED_MEM, "%spoints/scalars residency differs", who);
+    *owner = rp == RES_DEVICE ? dev_state_of(ctx, dp) : nullptr;
+    if (rp == RES_DEVICE && !*owner) return failf(ZC_ERR_MIXED_MEM, "%sdevice buffers do not belong to a device of this context", who);
+    return ZC_OK;
+}
+// The inputs of an MSM call to device D, which becomes the current device; an asynchronous failure of an earlier windowed-core
+// call surfaces here too.  Host arrays (on_device false) are uploaded on D.s() into D.scratch[0] (160-byte points) and
+// D.scratch[1] (40-byte scalars) and the pointers redirected; a null array is skipped (zc_msm_fixed: the points are the table's).
+int msm_stage(DevState& D, bool on_device, const u64** points, size_t npoints, const u64** scalars, size_t nscalars)
+{
+    if (int rc = ring_check(D)) return rc;
+    HIP_TRY(hipSetDevice(D.device));
+    if (on_device) return ZC_OK;
+    const u64** const arr[2] = {points, scalars};
+    const size_t bytes[2] = {npoints * 160, nscalars * 40};
+    for (int a = 0; a < 2; a++)
+        if (arr[a])
+            if (int rc = ensure(&D.scratch[a], &D.scratch_bytes[a], bytes[a])) return rc;
+    for (int a = 0; a < 2; a++) {
+        if (!arr[a]) continue;
+        HIP_TRY(hipMemcpyAsync(D.scratch[a], *arr[a], bytes[a], hipMemcpyHostToDevice, D.s()));
+        *arr[a] = (const u64*)D.scratch[a];
+    }
+    return ZC_OK;
+}
+
 // One device's shard of an MSM, inputs host (staged) or device (in place); the 160-byte sum stays
 // in device memory (*result), everything enqueued on ds.s().
 int msm_shard(DevState& ds, const uint64_t* points, const uint64_t* scalars, size_t cnt, bool on_device, const u64** result)
 {
-    if (int rc = ring_check(ds)) return rc;                  // an asynchronous failure of an earlier windowed-core call surfaces here too
-    HIP_TRY(hipSetDevice(ds.device));
-    const u64 *dP = points, *dK = scalars;
-    if (!on_device) {
-        int rc = ensure(&ds.scratch[0], &ds.scratch_bytes[0], cnt * 160);
-        if (rc) return rc;
-        rc = ensure(&ds.scratch[1], &ds.scratch_bytes[1], cnt * 40);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ds.scratch[0], points, cnt * 160, hipMemcpyHostToDevice, ds.s()));
-        HIP_TRY(hipMemcpyAsync(ds.scratch[1], scalars, cnt * 40, hipMemcpyHostToDevice, ds.s()));
-        dP = (const u64*)ds.scratch[0];
-        dK = (const u64*)ds.scratch[1];
-    }
-    return msm_on_device(ds, dP, dK, cnt, result);
+    if (int rc = msm_stage(ds, on_device, &points, cnt, &scalars, cnt)) return rc;
+    return msm_on_device(ds, points, scalars, cnt, result);
 }
 
 // ---------------------------------------------------------------- batched variable-base MSM (zc_msm_batch)
-// `batch` independent MSMs of n pairs each, instance-major.  Instances of at least this many pairs take the bucket regime
-// (every instance's windows are sort windows of one key sort; one bucket reduction and one parallel Horner step for all);
-// below it, batch n strict scalar multiplications and a pairwise fold per instance.  Sweep at 2^20 pairs in all
-// (tools/bench_msm_batch.py --sweep, profiles/r08_msm_batch_sweep.json): see DESIGN.md section 7.2.
-#ifndef ZC_MSM_BATCH_BUCKET_MIN_N
-#define ZC_MSM_BATCH_BUCKET_MIN_N 64
-#endif
-constexpr size_t MSM_BATCH_BUCKET_MIN_N = ZC_MSM_BATCH_BUCKET_MIN_N;
-// Window width of the bucket regime, per instance: the bucket sums cost n W additions and the reduction about 3.7 per bucket,
-// 2^(c-1) buckets per window: c minimises ceil(261 / c) (n + 3.7 2^(c-1)) (about 9 at n = 2^12).  The Horner step's chain is
-// shared by all instances, so it does not enter the per-instance cost.  ZC_MSM_WINDOW=c overrides, as for zc_msm.
-int msm_batch_window_bits(size_t n, const Tuning& tune)
-{
-    if (tune.msm_window >= zc::MSM_MIN_C && tune.msm_window <= zc::MSM_MAX_C) return tune.msm_window;
-    int best = zc::MSM_MIN_C;
-    double best_cost = 0;
-    for (int c = zc::MSM_MIN_C; c <= zc::MSM_MAX_C; c++) {
-        const double cost = (double)((zc::MSM_SCALAR_BITS + c - 1) / c) * ((double)n + 3.7 * (double)((size_t)1 << (c - 1)));
-        if (c == zc::MSM_MIN_C || cost < best_cost) best = c, best_cost = cost;
-    }
-    return best;
-}
-struct MsmBatchPlan {
-    bool buckets = false;          // false: batch n scalar multiplications + a pairwise fold per instance
-    int c = 0, W = 0;              // window bits and windows of the bucket regime (the limits are checked with them in both regimes)
-    bool affine = false;           // affine records (batch n >= 2^17 and 16-byte aligned points), else projective
-    int T = 0, TE = 8, seg = 0;    // run lengths (level 0, deeper levels), buckets per reduction segment
-    size_t m = 0, nb = 0, nseg = 0, nl0 = 0;   // list entries (batch n W), buckets (batch W 2^(c-1)), segments, level-0 lanes
-    int rec_bytes = 128;           // stride of the cached records
-    MsmSortPlan sort;
-};
-MsmBatchPlan msm_batch_plan(size_t n, size_t batch, bool points_aligned16, const Tuning& tune)
-{
-    MsmBatchPlan p;
-    if (n == 0 || batch == 0) return p;
-    p.c = msm_batch_window_bits(n, tune);
-    p.W = (zc::MSM_SCALAR_BITS + p.c - 1) / p.c;
-    if (n < MSM_BATCH_BUCKET_MIN_N) return p;
-    p.buckets = true;
-    const size_t nw = batch * (size_t)p.W;                    // sort windows
-    p.m = nw * n;
-    p.nb = nw << (p.c - 1);
-    p.sort = msm_sort_plan(n, p.c, (int)nw, tune);
-    p.affine = msm_affine(batch * n, tune) && points_aligned16;
-    p.rec_bytes = p.affine ? ZC_MSM_REC_STRIDE : 128;
-    p.T = msm_run_length(p.m, tune);
-    if (tune.msm_run_edges) p.TE = tune.msm_run_edges & ~1;
-    p.seg = tune.msm_seg ? tune.msm_seg : zc::msm_segment_buckets(p.nb);
-    while (p.seg > (1 << (p.c - 1))) p.seg >>= 1;          // a segment never spans windows
-    p.nseg = p.nb / (size_t)p.seg;
-    p.nl0 = (p.m + (size_t)p.T - 1) / (size_t)p.T;
-    return p;
-}
-// The index limits of a batch, checked before anything is allocated: record indices batch n < 2^31, pair indices
-// batch n W < 2^32, bucket keys batch W 2^(c-1) < 2^32 (c, W: the bucket regime's, whichever regime runs).
-int msm_batch_check(size_t n, size_t batch, const Tuning& tune, const char* who)
-{
-    if (n == 0 || batch == 0) return ZC_OK;
-    char msg[160];
-    const size_t lim31 = (size_t)1 << 31, lim32 = (size_t)1 << 32;
-    if (n >= lim31 || batch >= lim31 || n * batch >= lim31)
-        return snprintf(msg, sizeof msg, "%s: %zu instances x %zu pairs do not fit 31-bit record indices", who, batch, n), fail(ZC_ERR_BAD_ARG, msg);
-    const int c = msm_batch_window_bits(n, tune);
-    const size_t W = (size_t)((zc::MSM_SCALAR_BITS + c - 1) / c);
-    if (n * batch * W >= lim32)
-        return snprintf(msg, sizeof msg, "%s: %zu instances x %zu pairs x %zu windows do not fit 32-bit pair indices", who, batch, n, W), fail(ZC_ERR_BAD_ARG, msg);
-    if ((batch * W) << (c - 1) >= lim32)
-        return snprintf(msg, sizeof msg, "%s: %zu instances x %zu windows x 2^%d buckets do not fit 32-bit bucket keys", who, batch, W, c - 1), fail(ZC_ERR_BAD_ARG, msg);
-    return ZC_OK;
-}
-// The batch's sums, enqueued on D.s() without any host synchronisation: *result = batch canonical points in D.msm (valid until
-// the next MSM on this device).  batch >= 2, n >= 1, limits checked.
+// The batch's sums (`batch` independent MSMs of n pairs each, instance-major), enqueued on D.s() without any host
+// synchronisation: *result = batch canonical points in D.msm (valid until the next MSM on this device).  batch >= 2, n >= 1,
+// limits checked.  The regimes and the window width: zc_msm_plan.h, msm_batch_plan.
 int msm_batch_on_device(DevState& D, const u64* dP, const u64* dK, size_t n, size_t batch, const u64** result)
 {
     const Tuning& tune = D.tune;
-    const MsmBatchPlan bp = msm_batch_plan(n, batch, aligned16(dP), tune);
+    const MsmBucketPlan bp = msm_batch_plan(n, batch, aligned16(dP), tune.msm);
     const size_t cnt = n * batch;
     if (!bp.buckets) {
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv{pass ? (char*)D.msm : nullptr};
-            u64* prod = cv.take<u64>(cnt * 20);
-            u64* half = cv.take<u64>(batch * ((n + 1) / 2) * 20);
-            if (!pass) {
-                if (int rc = ensure(&D.msm, &D.msm_bytes, cv.off)) return rc;
-                continue;
-            }
-            scalar_mul_on_device(D, dP, dK, prod, cnt);
-            // every level halves every row: rows of n, ceil(n / 2), ... points, ping-pong between the two buffers
-            u64* cur = prod;
-            u64* nxt = half;
-            for (size_t len = n; len > 1; len = (len + 1) / 2) {
-                hipLaunchKernelGGL(zc::k_msm_fold_rows, dim3(grid_for(batch * ((len + 1) / 2))), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)cur, nxt, batch, len);
-                std::swap(cur, nxt);
-            }
-            *result = cur;
+        // two buffers of the workspace: the batch n products, and the other side of the folds' ping-pong
+        const size_t prod_bytes = (cnt * 160 + 255) & ~(size_t)255, half_bytes = (batch * ((n + 1) / 2) * 160 + 255) & ~(size_t)255;
+        if (int rc = ensure(&D.msm, &D.msm_bytes, prod_bytes + half_bytes)) return rc;
+        u64* cur = (u64*)D.msm;
+        u64* nxt = (u64*)((char*)D.msm + prod_bytes);
+        scalar_mul_on_device(D, dP, dK, cur, cnt);
+        // every level halves every row: rows of n, ceil(n / 2), ... points, ping-pong between the two buffers
+        for (size_t len = n; len > 1; len = (len + 1) / 2) {
+            hipLaunchKernelGGL(zc::k_msm_fold_rows, dim3(grid_for(batch * ((len + 1) / 2))), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)cur, nxt, batch, len);
+            std::swap(cur, nxt);
         }
+        *result = cur;
         HIP_TRY(hipGetLastError());
         return ZC_OK;
     }
     const int c = bp.c, W = bp.W;
-    const size_t m = bp.m, nb = bp.nb, nw = batch * (size_t)W;
-    const MsmSortPlan& plan = bp.sort;
-    const zc::u32 rec_words = (zc::u32)(bp.rec_bytes / 4);
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv{pass ? (char*)D.msm : nullptr};
-        zc::u32* digits = cv.take<zc::u32>(m);
-        uint2* pairs_a = cv.take<uint2>(m);
-        void* pairs_b = plan.passes == 1 ? nullptr : plan.packed ? (void*)cv.take<zc::u32>(m) : (void*)cv.take<uint2>(m);
-        zc::u32* sort_table = cv.take<zc::u32>(2 * plan.table_words);
-        zc::u32* sort_sums = cv.take<zc::u32>(plan.table_words / zc::SCAN_BLOCK_ELEMS + 1);
-        zc::u32* cached = cv.take<zc::u32>(cnt * 32);
-        zc::u32* buckets = cv.take<zc::u32>(nb * zc::MSM_RAW_WORDS);
-        uint8_t* present = cv.take<uint8_t>(nb);
-        zc::u32* ekeys[2] = {cv.take<zc::u32>(2 * bp.nl0), cv.take<zc::u32>(2 * bp.nl0)};
-        zc::u32* erecs[2] = {cv.take<zc::u32>(2 * bp.nl0 * zc::MSM_RAW_WORDS), cv.take<zc::u32>(2 * bp.nl0 * zc::MSM_RAW_WORDS)};
-        u64* seg_out = cv.take<u64>(bp.nseg * 20);
-        u64* fold_b = cv.take<u64>(bp.nseg * 20);
-        u64* out = cv.take<u64>(batch * 20);
-        if (!pass) {
-            if (int rc = ensure(&D.msm, &D.msm_bytes, cv.off)) return rc;
-            continue;
-        }
-        // one normalisation over all batch n points: it is per point, instance boundaries do not matter
-        if (bp.affine)
-            msm_prepare_affine(D.s(), dP, cached, cnt, tune, rec_words);
-        else
-            hipLaunchKernelGGL(aligned16(dP) ? zc::k_msm_prepare : zc::k_msm_prepare_lane, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dP, cached, cnt);
-        hipLaunchKernelGGL(zc::k_msm_fixed_digits, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, digits, n, batch, c, W);
-        HIP_TRY(hipMemsetAsync(present, 0, nb, D.s()));
-        if (int rc = msm_sort(D, D.s(), plan, 0, (int)nw, digits, pairs_a, pairs_b, sort_table, plan.table_words, sort_sums)) return rc;
-        hipLaunchKernelGGL(zc::k_msm_batch_rebase, dim3(grid_for(m)), dim3(zc::ZC_BLOCK), 0, D.s(), pairs_a, m, (zc::u32)nb, (zc::u32)((size_t)W << (c - 1)), (zc::u32)n);
-        const MsmReduceBufs rb{pairs_a, cached, rec_words, bp.affine, m, nb, buckets, present, {ekeys[0], ekeys[1]}, {erecs[0], erecs[1]}, c, bp.TE};
-        u64* sums = nullptr;
-        if (int rc = msm_reduce_windows(D, rb, 0, (int)nw, bp.T, bp.nl0, 0, nullptr, nullptr, 0, D.s(), nullptr, bp.seg, bp.nseg,
-                                        (size_t)ZC_MSM_SEG_QUAD, seg_out, fold_b, &sums))
-            return rc;
-        // Horner's rule over every instance's W window sums at once: 16 instances per 64-lane workgroup
-        hipLaunchKernelGGL(zc::k_msm_window_combine_batch, dim3((unsigned)((batch + 15) / 16)), dim3(64), 0, D.s(), (const u64*)sums, out, batch, W, c);
-        *result = out;
-        HIP_TRY(hipGetLastError());
-    }
+    MsmWorkspace ws;
+    if (int rc = msm_workspace(D, bp, cnt, batch, &ws)) return rc;
+    // one normalisation over all batch n points: it is per point, instance boundaries do not matter
+    if (bp.affine)
+        msm_prepare_affine(D.s(), dP, ws.cached, cnt, tune, (zc::u32)(bp.rec_bytes / 4));
+    else
+        hipLaunchKernelGGL(aligned16(dP) ? zc::k_msm_prepare : zc::k_msm_prepare_lane, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dP, ws.cached, cnt);
+    hipLaunchKernelGGL(zc::k_msm_fixed_digits, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, ws.digits, n, batch, c, W);
+    HIP_TRY(hipMemsetAsync(ws.present, 0, bp.nb, D.s()));
+    if (int rc = msm_sort(D, D.s(), bp.sort, 0, (int)bp.nw, ws.digits, ws.pairs_a, ws.pairs_b, ws.sort_table, bp.sort.table_words, ws.sort_sums)) return rc;
+    hipLaunchKernelGGL(zc::k_msm_batch_rebase, dim3(grid_for(bp.m)), dim3(zc::ZC_BLOCK), 0, D.s(), ws.pairs_a, bp.m, (zc::u32)bp.nb, (zc::u32)((size_t)W << (c - 1)), (zc::u32)n);
+    u64* sums = nullptr;
+    if (int rc = msm_reduce_windows(D, msm_reduce_bufs(bp, ws, ws.cached), msm_reduce_flat(bp, ws), &sums)) return rc;
+    // Horner's rule over every instance's W window sums at once: 16 instances per 64-lane workgroup
+    hipLaunchKernelGGL(zc::k_msm_window_combine_batch, dim3((unsigned)((batch + 15) / 16)), dim3(64), 0, D.s(), (const u64*)sums, ws.out, batch, W, c);
+    *result = ws.out;
+    HIP_TRY(hipGetLastError());
     return ZC_OK;
 }
 
@@ -2040,16 +1783,11 @@ static int gather_and_fold(zc_ctx* ctx, const std::vector<DevState*>& used, cons
 // worker thread per slot; device inputs: the owning slot); *result in device memory of *owner
 static int msm_local(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, size_t n, DevState** owner, const u64** result)
 {
-    Residency rp, rk;
-    int dp = -1, dk = -1;
-    residency_of(points, &rp, &dp);
-    residency_of(scalars, &rk, &dk);
-    if (rp != rk || (rp == RES_DEVICE && dp != dk)) return fail(ZC_ERR_MIXED_MEM, "points/scalars residency differs");
+    DevState* ds = nullptr;
+    if (int rc = msm_inputs_owner(ctx, points, scalars, "", &ds)) return rc;
     std::vector<DevState*> used;
     std::vector<const u64*> partial_ptr;
-    if (rp == RES_DEVICE) {
-        DevState* ds = dev_state_of(ctx, dp);
-        if (!ds) return fail(ZC_ERR_MIXED_MEM, "device buffers do not belong to a device of this context");
+    if (ds) {
         const u64* part = nullptr;
         int rc = msm_shard(*ds, points, scalars, n, true, &part);
         if (rc) return rc;
@@ -2116,39 +1854,27 @@ int zc_test_msm_sort(zc_ctx* ctx, const uint64_t* scalars, size_t n, int c, uint
     std::lock_guard<std::mutex> lock(ctx->mu);
     DevState& D = ctx->devs[0];
     HIP_TRY(hipSetDevice(D.device));
-    const int W = (zc::MSM_SCALAR_BITS + c - 1) / c;
-    const size_t m = n * (size_t)W;
-    if (m > 0xFFFFFFFFull) return fail(ZC_ERR_BAD_ARG, "zc_test_msm_sort: too many pairs");
-    const MsmSortPlan plan = msm_sort_plan(n, c, W, D.tune);
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv{pass ? (char*)D.msm : nullptr};
-        zc::u32* digits = cv.take<zc::u32>(m);
-        uint2* pairs_a = cv.take<uint2>(m);
-        void* pairs_b = plan.passes == 1 ? nullptr : plan.packed ? (void*)cv.take<zc::u32>(m) : (void*)cv.take<uint2>(m);
-        zc::u32* table = cv.take<zc::u32>(2 * plan.table_words);
-        zc::u32* sums = cv.take<zc::u32>(plan.table_words / zc::SCAN_BLOCK_ELEMS + 1);
-        if (!pass) {
-            int rc = ensure(&D.msm, &D.msm_bytes, cv.off);
-            if (rc) return rc;
-            continue;
-        }
-        hipLaunchKernelGGL(zc::k_msm_digits, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)scalars, digits, n, c, W);
-        // ZC_MSM_GROUPS that adds up to the windows: every group sorted on its own, top group first (as msm_on_device does)
-        int gsum = 0;
-        for (int g = 0; g < D.tune.msm_ngroups; g++) gsum += D.tune.msm_groups[g];
-        if (D.tune.msm_ngroups >= 2 && gsum == W) {
-            int top = W;
-            for (int g = 0; g < D.tune.msm_ngroups; g++) {
-                top -= D.tune.msm_groups[g];
-                if (int rc = msm_sort(D, D.s(), plan, top, D.tune.msm_groups[g], digits, pairs_a, pairs_b, table, plan.table_words, sums)) return rc;
-            }
-        } else if (int rc = msm_sort(D, D.s(), plan, 0, W, digits, pairs_a, pairs_b, table, plan.table_words, sums)) {
-            return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(out_pairs, pairs_a, m * sizeof(uint2), hipMemcpyDeviceToDevice, D.s()));
-        HIP_TRY(hipStreamSynchronize(D.s()));
-        HIP_TRY(hipGetLastError());
+    const int W = zc::msm_windows(c);
+    if (zc::msm_index_limit(0, zc::msm_sat_mul(n, (size_t)W), 0)) return fail(ZC_ERR_BAD_ARG, "zc_test_msm_sort: too many pairs");
+    const zc::MsmKnobs& knobs = D.tune.msm;
+    const MsmBucketPlan bp = msm_bucket_plan(n, (size_t)W, c, false, knobs);
+    const MsmSortPlan& plan = bp.sort;
+    MsmWorkspace ws;
+    if (int rc = msm_workspace(D, bp, 0, 0, &ws, true)) return rc;
+    hipLaunchKernelGGL(zc::k_msm_digits, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)scalars, ws.digits, n, c, W);
+    // ZC_MSM_GROUPS that adds up to the windows: every group sorted on its own, top group first (the per-group sort that was
+    // measured against msm_on_device's one sort)
+    int gsum = 0;
+    for (int g = 0; g < knobs.ngroups; g++) gsum += knobs.groups[g];
+    const bool split = knobs.ngroups >= 2 && gsum == W;
+    for (int g = 0, top = W; top > 0; g++) {
+        const int nw = split ? knobs.groups[g] : W;
+        top -= nw;
+        if (int rc = msm_sort(D, D.s(), plan, top, nw, ws.digits, ws.pairs_a, ws.pairs_b, ws.sort_table, plan.table_words, ws.sort_sums)) return rc;
     }
+    HIP_TRY(hipMemcpyAsync(out_pairs, ws.pairs_a, bp.m * sizeof(uint2), hipMemcpyDeviceToDevice, D.s()));
+    HIP_TRY(hipStreamSynchronize(D.s()));
+    HIP_TRY(hipGetLastError());
     return ZC_OK;
 }
 // Test hook: the w-NAF's odd-multiples table as the device built it, as 125 points in DEVICE memory of slot 0.
@@ -2188,16 +1914,23 @@ long long zc_test_staged_launches(zc_ctx* ctx)
 // record (112 / 128), [4] run length of the bucket-sum kernel (window groups: the top group's), [5] buckets per reduction
 // segment, [6] sort passes, [7] window groups G, [8] record STRIDE in bytes (what a gather touches: one 128-byte line),
 // [9..12] windows per group (top group first), [13..16] run length per group.
+static int msm_plan_report(zc_ctx* ctx, const char* who, size_t n, int points_aligned16, int32_t (&v)[17])
+{
+    const MsmPlan p = msm_plan(n, points_aligned16 != 0, ctx->devs[0].tune.msm);
+    if (p.bad_groups) return failf(ZC_ERR_BAD_ARG, "%s: ZC_MSM_GROUPS does not add up to this shard's window count", who);
+    const bool b = p.buckets;
+    const int32_t w[17] = {p.c, p.W, p.affine ? 1 : 0, b ? (p.affine ? zc::MSM_AFF_WORDS * 4 : 128) : 0, b ? p.gT[0] : 0, p.seg, p.sort.passes, b ? p.G : 0, b ? p.rec_bytes : 0,
+                           p.gw[0], p.gw[1], p.gw[2], p.gw[3], p.gT[0], p.gT[1], p.gT[2], p.gT[3]};
+    memcpy(v, w, sizeof w);
+    return ZC_OK;
+}
 int zc_msm_plan(zc_ctx* ctx, size_t n, int points_aligned16, int32_t* out, int nout)
 {
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     REQUIRE(out);
     if (nout < 8) return fail(ZC_ERR_BAD_ARG, "zc_msm_plan: nout < 8");
-    const MsmPlan p = msm_plan(n, points_aligned16 != 0, ctx->devs[0].tune);
-    if (p.bad_groups) return fail(ZC_ERR_BAD_ARG, "zc_msm_plan: ZC_MSM_GROUPS does not add up to this shard's window count");
-    const bool b = p.buckets;
-    const int32_t v[17] = {p.c, p.W, p.affine ? 1 : 0, b ? (p.affine ? zc::MSM_AFF_WORDS * 4 : 128) : 0, b ? p.gT[0] : 0, p.seg, p.sort.passes, b ? p.G : 0, b ? p.rec_bytes : 0,
-                           p.gw[0], p.gw[1], p.gw[2], p.gw[3], p.gT[0], p.gT[1], p.gT[2], p.gT[3]};
+    int32_t v[17];
+    if (int rc = msm_plan_report(ctx, "zc_msm_plan", n, points_aligned16, v)) return rc;
     memcpy(out, v, sizeof(int32_t) * (size_t)std::min(nout, 17));
     return ZC_OK;
 }
@@ -2290,56 +2023,27 @@ int zc_msm_fixed(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, size_t batch
     const MsmBases& t = it->second;
     const size_t n = t.n;
     const int c = t.c;
-    if (batch >= ((size_t)1 << 32) / (n * (size_t)t.W) + 1 || batch * n * (size_t)t.W >= ((size_t)1 << 32))
-        return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x n x W does not fit 32-bit pair indices");
-    if (batch >= ((size_t)1 << (33 - c)))
-        return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x 2^(c-1) buckets do not fit 32-bit bucket keys");
+    const zc::MsmLimit limit = zc::msm_index_limit(0, zc::msm_sat_mul(batch, n * (size_t)t.W), zc::msm_sat_mul(batch, (size_t)1 << (c - 1)));
+    if (limit == zc::MSM_LIMIT_PAIRS) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x n x W does not fit 32-bit pair indices");
+    if (limit == zc::MSM_LIMIT_KEYS) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x 2^(c-1) buckets do not fit 32-bit bucket keys");
     DevState& D = ctx->devs[(size_t)t.slot];
     Residency rk;
     int dk = -1;
     residency_of(scalars, &rk, &dk);
     if (rk == RES_DEVICE && dk != D.device) return fail(ZC_ERR_MIXED_MEM, "zc_msm_fixed: scalars on another device than the table");
-    if (int rc = ring_check(D)) return rc;
-    HIP_TRY(hipSetDevice(D.device));
     const u64* dK = scalars;
-    if (rk == RES_HOST) {
-        if (int rc = ensure(&D.scratch[1], &D.scratch_bytes[1], batch * n * 40)) return rc;
-        HIP_TRY(hipMemcpyAsync(D.scratch[1], scalars, batch * n * 40, hipMemcpyHostToDevice, D.s()));
-        dK = (const u64*)D.scratch[1];
-    }
-    const MsmFixedPlan fp = msm_fixed_plan(n, c, batch, D.tune);
-    const MsmSortPlan& plan = fp.sort;
-    const size_t m = fp.m, nb = fp.nb;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv{pass ? (char*)D.msm : nullptr};
-        zc::u32* digits = cv.take<zc::u32>(m);
-        uint2* pairs_a = cv.take<uint2>(m);
-        void* pairs_b = plan.passes == 1 ? nullptr : plan.packed ? (void*)cv.take<zc::u32>(m) : (void*)cv.take<uint2>(m);
-        zc::u32* sort_table = cv.take<zc::u32>(2 * plan.table_words);
-        zc::u32* sort_sums = cv.take<zc::u32>(plan.table_words / zc::SCAN_BLOCK_ELEMS + 1);
-        zc::u32* buckets = cv.take<zc::u32>(nb * zc::MSM_RAW_WORDS);
-        uint8_t* present = cv.take<uint8_t>(nb);
-        zc::u32* ekeys[2] = {cv.take<zc::u32>(2 * fp.nl0), cv.take<zc::u32>(2 * fp.nl0)};
-        zc::u32* erecs[2] = {cv.take<zc::u32>(2 * fp.nl0 * zc::MSM_RAW_WORDS), cv.take<zc::u32>(2 * fp.nl0 * zc::MSM_RAW_WORDS)};
-        u64* seg_out = cv.take<u64>(fp.nseg * 20);
-        u64* fold_b = cv.take<u64>(fp.nseg * 20);
-        if (!pass) {
-            if (int rc = ensure(&D.msm, &D.msm_bytes, cv.off)) return rc;
-            continue;
-        }
-        hipLaunchKernelGGL(zc::k_msm_fixed_digits, dim3(grid_for(batch * n)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, digits, n, batch, c, t.W);
-        HIP_TRY(hipMemsetAsync(present, 0, nb, D.s()));
-        if (int rc = msm_sort(D, D.s(), plan, 0, (int)batch, digits, pairs_a, pairs_b, sort_table, plan.table_words, sort_sums)) return rc;
-        const MsmReduceBufs rb{pairs_a, (const zc::u32*)t.recs, (zc::u32)(ZC_MSM_REC_STRIDE / 4), true, m, nb, buckets, present,
-                               {ekeys[0], ekeys[1]}, {erecs[0], erecs[1]}, c, fp.TE};
-        u64* sums = nullptr;
-        if (int rc = msm_reduce_windows(D, rb, 0, (int)batch, fp.T, fp.nl0, 0, nullptr, nullptr, 0, D.s(), nullptr, fp.seg, fp.nseg,
-                                        (size_t)ZC_MSM_SEG_QUAD, seg_out, fold_b, &sums))
-            return rc;
-        // the folds leave the batch's sums as canonical extended points, one per vector in order
-        HIP_TRY(hipMemcpyAsync(out_points, sums, batch * 160, hipMemcpyDeviceToHost, D.s()));
-        HIP_TRY(hipStreamSynchronize(D.s()));
-    }
+    if (int rc = msm_stage(D, rk == RES_DEVICE, nullptr, 0, &dK, batch * n)) return rc;
+    const MsmBucketPlan fp = msm_fixed_plan(n, c, batch, D.tune.msm);
+    MsmWorkspace ws;
+    if (int rc = msm_workspace(D, fp, 0, 0, &ws)) return rc;
+    hipLaunchKernelGGL(zc::k_msm_fixed_digits, dim3(grid_for(batch * n)), dim3(zc::ZC_BLOCK), 0, D.s(), dK, ws.digits, n, batch, c, t.W);
+    HIP_TRY(hipMemsetAsync(ws.present, 0, fp.nb, D.s()));
+    if (int rc = msm_sort(D, D.s(), fp.sort, 0, (int)batch, ws.digits, ws.pairs_a, ws.pairs_b, ws.sort_table, fp.sort.table_words, ws.sort_sums)) return rc;
+    u64* sums = nullptr;
+    if (int rc = msm_reduce_windows(D, msm_reduce_bufs(fp, ws, (const zc::u32*)t.recs), msm_reduce_flat(fp, ws), &sums)) return rc;
+    // the folds leave the batch's sums as canonical extended points, one per vector in order
+    HIP_TRY(hipMemcpyAsync(out_points, sums, batch * 160, hipMemcpyDeviceToHost, D.s()));
+    HIP_TRY(hipStreamSynchronize(D.s()));
     return ZC_OK;
 }
 
@@ -2353,7 +2057,7 @@ int zc_msm_fixed_plan(zc_ctx* ctx, size_t n, int window_bits, int32_t* out, int 
     if (nout < 8) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed_plan: nout < 8");
     int c = 0, W = 0;
     if (int rc = msm_fixed_check(n, window_bits, &c, &W, "zc_msm_fixed_plan")) return rc;
-    const MsmFixedPlan p = msm_fixed_plan(n, c, 1, ctx->devs[0].tune);
+    const MsmBucketPlan p = msm_fixed_plan(n, c, 1, ctx->devs[0].tune.msm);
     const size_t mib = (n * (size_t)W * ZC_MSM_REC_STRIDE + ((size_t)1 << 20) - 1) >> 20;
     const int32_t v[8] = {c, W, ZC_MSM_REC_STRIDE, p.T, p.seg, p.sort.passes, (int32_t)mib, 1};
     memcpy(out, v, sizeof v);
@@ -2374,35 +2078,16 @@ int zc_msm_batch(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, s
         return ZC_OK;
     }
     if (int rc = msm_batch_check(n, batch, ctx->devs[0].tune, "zc_msm_batch")) return rc;
-    Residency rp, rk;
-    int dp = -1, dk = -1;
-    residency_of(points, &rp, &dp);
-    residency_of(scalars, &rk, &dk);
-    if (rp != rk || (rp == RES_DEVICE && dp != dk)) return fail(ZC_ERR_MIXED_MEM, "zc_msm_batch: points/scalars residency differs");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    DevState* ds = &ctx->devs[0];
-    if (rp == RES_DEVICE) {
-        ds = dev_state_of(ctx, dp);
-        if (!ds) return fail(ZC_ERR_MIXED_MEM, "zc_msm_batch: device buffers do not belong to a device of this context");
-    }
-    DevState& D = *ds;
-    const bool on_device = rp == RES_DEVICE;
+    DevState* owner = nullptr;
+    if (int rc = msm_inputs_owner(ctx, points, scalars, "zc_msm_batch: ", &owner)) return rc;
+    DevState& D = owner ? *owner : ctx->devs[0];
     const u64* res = nullptr;
     if (batch == 1) {
-        if (int rc = msm_shard(D, points, scalars, n, on_device, &res)) return rc;
+        if (int rc = msm_shard(D, points, scalars, n, owner != nullptr, &res)) return rc;
     } else {
-        if (int rc = ring_check(D)) return rc;
-        HIP_TRY(hipSetDevice(D.device));
         const u64 *dP = points, *dK = scalars;
-        const size_t cnt = n * batch;
-        if (!on_device) {
-            if (int rc = ensure(&D.scratch[0], &D.scratch_bytes[0], cnt * 160)) return rc;
-            if (int rc = ensure(&D.scratch[1], &D.scratch_bytes[1], cnt * 40)) return rc;
-            HIP_TRY(hipMemcpyAsync(D.scratch[0], points, cnt * 160, hipMemcpyHostToDevice, D.s()));
-            HIP_TRY(hipMemcpyAsync(D.scratch[1], scalars, cnt * 40, hipMemcpyHostToDevice, D.s()));
-            dP = (const u64*)D.scratch[0];
-            dK = (const u64*)D.scratch[1];
-        }
+        if (int rc = msm_stage(D, owner != nullptr, &dP, n * batch, &dK, n * batch)) return rc;
         if (int rc = msm_batch_on_device(D, dP, dK, n, batch, &res)) return rc;
     }
     HIP_TRY(hipSetDevice(D.device));
@@ -2422,17 +2107,15 @@ int zc_msm_batch_plan(zc_ctx* ctx, size_t n, size_t batch, int points_aligned16,
     if (nout < 8) return fail(ZC_ERR_BAD_ARG, "zc_msm_batch_plan: nout < 8");
     const Tuning& tune = ctx->devs[0].tune;
     if (int rc = msm_batch_check(n, batch, tune, "zc_msm_batch_plan")) return rc;
-    int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (batch == 1) {
-        const MsmPlan p = msm_plan(n, points_aligned16 != 0, tune);
-        if (p.bad_groups) return fail(ZC_ERR_BAD_ARG, "zc_msm_batch_plan: ZC_MSM_GROUPS does not add up to this shard's window count");
-        const int32_t w[8] = {p.buckets ? 1 : 0, p.c, p.W, p.affine ? 1 : 0, p.buckets ? p.gT[0] : 0, p.seg, p.sort.passes, p.buckets ? p.rec_bytes : 0};
-        memcpy(v, w, sizeof v);
-    } else {
-        const MsmBatchPlan p = msm_batch_plan(n, batch, points_aligned16 != 0, tune);
-        const int32_t w[8] = {p.buckets ? 1 : 0, p.c, p.W, p.affine ? 1 : 0, p.T, p.seg, p.sort.passes, p.buckets ? p.rec_bytes : 0};
-        memcpy(v, w, sizeof v);
+        int32_t s[17];                                       // zc_msm_plan's entries: [7] window groups (0 below the bucket threshold)
+        if (int rc = msm_plan_report(ctx, "zc_msm_batch_plan", n, points_aligned16, s)) return rc;
+        const int32_t v[8] = {s[7] ? 1 : 0, s[0], s[1], s[2], s[4], s[5], s[6], s[8]};
+        memcpy(out, v, sizeof v);
+        return ZC_OK;
     }
+    const MsmBucketPlan p = msm_batch_plan(n, batch, points_aligned16 != 0, tune.msm);
+    const int32_t v[8] = {p.buckets ? 1 : 0, p.c, p.W, p.affine ? 1 : 0, p.T, p.seg, p.sort.passes, p.buckets ? p.rec_bytes : 0};
     memcpy(out, v, sizeof v);
     return ZC_OK;
 }

@@ -229,3 +229,35 @@ def test_deterministic_and_interleaved(eng, oracle, crossover):
             assert all(eng.ed_eq(got[b:b + 1], want[b])[0] == 1 for b in range(batch))
             assert eng.ed_eq(fx[0:1], want[0])[0] == 1
             check_vs_oracle(oracle, got2, Q, L, range(4))
+
+
+def test_one_workspace_serves_every_pipeline(oracle):
+    """zc_msm, zc_msm_batch and zc_msm_fixed lay their buffers out in ONE device allocation, each from its own plan.  On a
+    fresh context, in this order: the smallest bucket-regime shape of each (4096 pairs; 3 instances of 64; 2 vectors over 64
+    bases), a zc_msm of 8192 + 5 pairs, which needs more than the allocation holds and so replaces it, then the first three
+    again.  Every sum is the oracle's group element, every repeat has the limbs of its first run."""
+    import dusk_zerocaf_amd as z
+    e = z.Engine()
+    try:
+        big = 8192 + 5
+        P = batch_points(e, big, 1, V.SEED + 480)[0]
+        K = batch_scalars(big, 1, V.SEED + 481)[0]
+        Pb = batch_points(e, 64, 3, V.SEED + 482)
+        Kb = batch_scalars(64, 3, V.SEED + 483)
+        Kf = batch_scalars(64, 2, V.SEED + 484)
+        assert e.msm_plan(4096)["window_bits"] and not e.msm_plan(4095)["window_bits"]
+        assert e.msm_batch_plan(64, 3)["regime"] == "buckets" and e.msm_batch_plan(63, 3)["regime"] == "scalar_mul"
+        with e.msm_bases(Pb[0]) as tb:
+            def three():
+                return e.msm(P[:4096], K[:4096]), e.msm_batch(Pb, Kb), tb.msm(Kf)
+            m1, b1, f1 = three()
+            g = e.msm(P, K)
+            m2, b2, f2 = three()
+        same_point(oracle, m1, oracle.msm_naive_mt(P[:4096], K[:4096]))
+        check_vs_oracle(oracle, b1, Pb, Kb, range(3))
+        for v in range(2):
+            same_point(oracle, f1[v], oracle.msm_naive_mt(Pb[0], Kf[v]))
+        same_point(oracle, g, oracle.msm_naive_mt(P, K))
+        assert np.array_equal(m1, m2) and np.array_equal(b1, b2) and np.array_equal(f1, f2)
+    finally:
+        e.close()

@@ -90,6 +90,7 @@ SIGNATURES = {
     "zc_msm_batch": [_u64p, _u64p, _n, _n, _u64p],
     "zc_msm_batch_plan": [_n, _n, C.c_int, C.POINTER(C.c_int32), C.c_int],
     "zc_ed_lincomb": [_u64p, _u64p, _n, _u64p, _n],
+    "zc_ris_lincomb": [_u8p, _u64p, _n, _u64p, _u8p, _u8p, _n],
     "zc_comm_init": [_u8p, C.c_int, C.c_int],
     "zc_comm_destroy": [],
     "zc_comm_size": [C.POINTER(C.c_int)],

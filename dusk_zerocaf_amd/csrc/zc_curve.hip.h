@@ -1326,6 +1326,112 @@ ZC_DI pt lincomb_strict(const u64* __restrict__ points, const u64* __restrict__ 
     return acc;
 }
 
+// ---------------------------------------------------------------- fixed-base comb of the curve basepoint (per-lane parts)
+// T[w][j] = (j+1) * 256^w * B, 33 windows x 128 cached affine points (zc_kernels.hip.h: k_base_table_build and the kernels
+// that read the table); here so that the host-emulation tier drives the same functions.
+constexpr int ZC_BASE_WINDOWS = 33;                      // signed radix-256 digits of a 260-bit scalar (+ carry)
+constexpr int ZC_BASE_ENTRIES = 128;                     // |digit| = 1 .. 128
+// column j (0..127) of the table: (j+1) * 256^w * B for w = 0..32
+ZC_DI void base_table_column(u32* __restrict__ table, int j)
+{
+    pt B;
+    B.X = fe_const<FP>(ModP::BASE_X_M);
+    B.Y = fe_const<FP>(ModP::BASE_Y_M);
+    B.Z = fe_one_m<FP>();
+    B.T = fe_const<FP>(ModP::BASE_T_M);
+    pt P = B;
+    for (int a = 0; a < ZC_BASE_ENTRIES - 1; a++) {
+        const pt s = pt_add(P, B);
+        P = pt_select(a < j, s, P);                       // P = (j+1) * B
+    }
+    for (int w = 0; w < ZC_BASE_WINDOWS; w++) {
+        // entries are normalised to Z = 1 once, here, so every later addition against them is mixed
+        const fe zi = fp_invert(P.Z);
+        pt A;
+        A.X = fp_mul(P.X, zi);
+        A.Y = fp_mul(P.Y, zi);
+        A.Z = fe_one_m<FP>();
+        A.T = fp_mul(A.X, A.Y);
+        niels_store(table + 32 * (w * ZC_BASE_ENTRIES + j), niels_from_pt(A));
+#pragma unroll 1
+        for (int t = 0; t < 8; t++) P = pt_add(P, P);
+    }
+}
+// Signed radix-256 digits of the 260-bit scalar, d_i in [-128, 128), 33 digits (carry included), stored as
+// bytes at dig[i * stride]; returns the index of the highest non-zero digit or -1.
+ZC_DI int scalar_digits256(int8_t* __restrict__ dig, int stride, const u64 (&l)[5])
+{
+    u32 w[9];
+    int nb;
+    {
+        u32 tmp[9];
+        scalar_to_words(tmp, 1, l, nb);
+#pragma unroll
+        for (int k = 0; k < 9; k++) w[k] = tmp[k];
+    }
+    int carry = 0, top = -1;
+    for (int i = 0; i < ZC_BASE_WINDOWS; i++) {
+        int d = (int)((w[i >> 2] >> ((i & 3) * 8)) & 255u) + carry;
+        carry = d >= 128;
+        d -= carry << 8;
+        dig[i * stride] = (int8_t)d;
+        if (d != 0) top = i;
+    }
+    return top;
+}
+ZC_DI pt base_mul(const u32* __restrict__ table, const int8_t* __restrict__ dig, int stride, int top)
+{
+    pt Q = pt_identity();
+    for (int w = top; w >= 0; w--) {
+        const int d = dig[w * stride];
+        const int mag = d < 0 ? -d : d;
+        niels c = niels_identity();
+        if (mag != 0) c = niels_load(table + 32 * (w * ZC_BASE_ENTRIES + mag - 1));
+        Q = pt_add_cached<false, true>(Q, niels_cond_neg(d < 0, c));     // table entries and the identity have z = 1
+    }
+    return Q;
+}
+// The same 33 digits, not stored: the scalar is kept as v + 0x80..80 (33 bytes of 0x80: nine words) and digit i = byte i - 128.
+// Adding 128 to every byte runs the very carry chain of scalar_digits256 (a byte plus its carry-in reaches 128 exactly when
+// the sum below overflows into the next byte) -- scalar_recode16's argument in radix 256; 36 bytes per scalar.
+// Returns the index of the highest non-zero digit or -1.
+ZC_DI int scalar_recode256(u32* __restrict__ rw, int stride, const u64 (&l)[5])
+{
+    u32 w[9];
+    int nb;
+    scalar_to_words(w, 1, l, nb);
+    u64 c = 0;
+    int top = -1;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const u32 halves = k < 8 ? 0x80808080u : 0x80u;  // v < 2^260: byte 32 is at most 15, the sum stays below 256^33
+        c += (u64)w[k] + halves;
+        const u32 r = (u32)c;
+        c >>= 32;
+        rw[k * stride] = r;
+        const u32 x = r ^ halves;                         // a byte of x is zero where the digit is
+        if (x) top = 4 * k + ((31 - __builtin_clz(x)) >> 3);
+    }
+    ZC_ASSERT(c == 0 && top < ZC_BASE_WINDOWS);
+    return top;
+}
+ZC_DI int recoded_digit256(const u32* __restrict__ rw, int stride, int i)
+{
+    return (int)((rw[(i >> 2) * stride] >> ((i & 3) * 8)) & 255u) - 128;
+}
+// Q + k * B: base_mul's additions on top of a running sum instead of the identity, digits read from scalar_recode256's words.
+ZC_DI pt base_mul_onto(pt Q, const u32* __restrict__ table, const u32* __restrict__ rw, int stride, int top)
+{
+    for (int w = top; w >= 0; w--) {
+        const int d = recoded_digit256(rw, stride, w);
+        const int mag = d < 0 ? -d : d;
+        niels c = niels_identity();
+        if (mag != 0) c = niels_load(table + 32 * (w * ZC_BASE_ENTRIES + mag - 1));
+        Q = pt_add_cached<false, true>(Q, niels_cond_neg(d < 0, c));
+    }
+    return Q;
+}
+
 // ---------------------------------------------------------------- byte codecs
 // plain 256-bit value <= (p-1)/2 ?  (is_positive on the raw decoded limbs, ristretto.rs:104-114)
 ZC_DI bool words256_is_positive(const fe& raw)
@@ -1400,6 +1506,54 @@ ZC_DI bool ris_eq(const pt& a, const pt& b)
     const bool e1 = fp_eq(fp_mul(a.X, b.Y), fp_mul(a.Y, b.X));
     const bool e2 = fp_eq(fp_mul(a.X, b.X), fp_mul(a.Y, b.Y));
     return e1 || e2;
+}
+
+// ---------------------------------------------------------------- wire-format linear combinations (zc_ris_lincomb)
+// encode(k_B * B + sum_j k_j * decode(E_j)): the per-lane steps of k_ris_lincomb (zc_kernels.hip.h), also driven by the host
+// emulation.  ris_lincomb_decode: one term's encoding -> its point (Z = 1, on the curve and T Z = X Y by construction), parked
+// as X | Y | T (27 words) in the first record of the term's table; returns the accept flag.  ris_lincomb_table: that point
+// -> the table {1P..8P}, which overwrites it.  An undecodable lane builds a table of arbitrary field elements -- its row is
+// discarded, the arithmetic has no data-dependent control flow.
+template <class TABLE>
+ZC_DI bool ris_lincomb_decode(const u64 (&w)[4], const TABLE table)
+{
+    pt P;
+    const bool dec = ris_decompress(P, w);
+    u32* e = table.entry(0);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        e[k] = P.X.v[k];
+        e[9 + k] = P.Y.v[k];
+        e[18 + k] = P.T.v[k];
+    }
+    return dec;
+}
+template <class TABLE>
+ZC_DI void ris_lincomb_table(const TABLE table)
+{
+    pt P;
+    const u32* e = table.entry(0);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        P.X.v[k] = e[k];
+        P.Y.v[k] = e[9 + k];
+        P.T.v[k] = e[18 + k];
+    }
+    P.Z = fe_one_m<FP>();
+    fast_table_build(P, table);
+}
+// The shared doubling chain over the terms' tables (top: the highest non-zero digit over the row's terms -- and, in the
+// kernel, over the wave).  The basepoint term follows as base_mul_onto, which needs no table slot.
+template <class TABLE>
+ZC_DI pt ris_lincomb_sum(const TABLE table, const u32* __restrict__ rw, int stride, int terms, int top)
+{
+    return zc_small_launch() ? lincomb_window_loop<true>(table, rw, stride, terms, top) : lincomb_window_loop<false>(table, rw, stride, terms, top);
+}
+// The row's 32 output bytes as four words: the encoding of Q, zeros where a term did not decode.
+ZC_DI void ris_lincomb_encode(u64 (&w)[4], const pt& Q, bool dec)
+{
+    fe_to_words256(w, ris_compress(pt_select(dec, Q, pt_identity())));
+    if (!dec) w[0] = w[1] = w[2] = w[3] = 0;
 }
 
 // Edwards -> affine (edwards.rs:1071-1092).  ok = Z != 0 (the reference panics there).

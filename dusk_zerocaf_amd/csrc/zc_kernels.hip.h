@@ -1141,6 +1141,82 @@ ZC_KERNEL_3W void k_ris_roundtrip_mul_fast(const uint8_t* in, const u64* k, uint
         if (ok) ok[i_late] = dec ? 1 : 0;
     }
 }
+// ---- wire-format linear combinations: out[i] = encode(kb[i] * B + sum_j k[i][j] * decode(in[i][j])) (zc_ris_lincomb) ----------
+// k_ed_lincomb with the codecs fused in, one row per lane: the terms' encodings are decoded into their tables (no point
+// array exists: a decoded point waits as 27 words in its own table's first record, which the build then overwrites) and
+// the sum leaves as 32 bytes.  Decoding and table building are two `unroll 1` loops on purpose: in one loop the compiler
+// hoists the field constants of both bodies (some 500 scalar registers' worth) in front of it, parks them in vector-register
+// lanes and the body then spills 80 vector registers to scratch; apart, the kernel keeps the 3-waves budget without scratch.  Ring geometry and LDS layout are k_ed_lincomb's; the base
+// scalar (kb != nullptr) takes the scalar slot behind the terms', recoded in radix 256 (scalar_recode256), and its 33 mixed
+// additions from the comb table `base` follow the window loop, after the slot is given back.  terms + (kb != nullptr) <= 8.
+// A row with an undecodable term yields 32 zero bytes and ok = 0 whatever its scalars; it contributes no window to the
+// wave's top.  Decoded points are on the curve with T Z = X Y, so there is no second pass.
+ZC_KERNEL_3W void k_ris_lincomb(const uint8_t* in, const u64* k, u32 terms, const u64* kb, uint8_t* out, uint8_t* ok, const u32* base,
+                                u32* table, u32* ring, u32 ring_slots, u32 units_per_xcd, u32 slot_units, u32 n)
+{
+    extern __shared__ u32 lincomb_rw[];                    // 9 * (terms + (kb != nullptr)) * blockDim.x words
+    const u32 block = blockDim.x;
+    const u32 wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // The row's number is formed afresh wherever it is needed, from the wave's number (an SGPR since the first instruction)
+    // and v_mbcnt: nothing derived from threadIdx.x stays live across a decode (see k_ris_roundtrip_mul_fast).
+    const u32 wave_first = blockIdx.x * block + wave_in_block * 64u;
+    __shared__ u32 hold[ZC_BLOCK / 64];
+    const ring_table got = ring_acquire(table, ring, hold + wave_in_block, ring_slots);
+    if (!got.base) {                                       // the wave gave up waiting for its table slot (wave-uniform): poison, no barrier follows
+        const u32 i = wave_first + lane_id_fresh();
+        if (i < n) {
+            const u64 ones[4] = {~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0};
+            store_words256(out + 32 * (size_t)i, ones);
+            if (ok) ok[i] = 0;
+        }
+        return;
+    }
+    const u32 named = (u32)((size_t)(got.base - table) / (64 * 256));          // xcc * RING_SLOTS + slot (wave-uniform)
+    const u32 xcc = named / RING_SLOTS, slot = named % RING_SLOTS;
+    const ring_table_terms mine{table + (size_t)(xcc * units_per_xcd + slot * slot_units) * (64 * 256)};
+    // the points first: the only per-lane value that survives a decode is the accept flag
+    bool dec = true;
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) {
+        const u32 row = wave_first + lane_id_fresh();
+        u64 w[4];
+        load_words256(w, in + 32 * ((size_t)(row < n ? row : 0) * terms + j));
+        dec = ris_lincomb_decode(w, mine.term((int)j)) && dec;
+    }
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) ris_lincomb_table(mine.term((int)j));
+    // then the scalars, recoded into LDS
+    const u32 tid = wave_in_block * 64u + lane_id_fresh();
+    const u32 i = blockIdx.x * block + tid;
+    const bool valid = i < n;
+    const size_t first = (size_t)(valid ? i : 0) * terms;  // the row's first record (n * terms < 2^31)
+    int top = -1, base_top = -1;
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) {
+        u64 l[5];
+        load_scalar(l, k + 5 * (first + j));
+        const int tj = scalar_recode16(lincomb_rw + 9 * j * block + tid, (int)block, l);
+        top = tj > top ? tj : top;
+    }
+    if (kb) {
+        u64 l[5];
+        load_scalar(l, kb + 5 * (size_t)(valid ? i : 0));
+        base_top = scalar_recode256(lincomb_rw + 9 * terms * block + tid, (int)block, l);
+    }
+    if (!valid || !dec) top = base_top = -1;
+    top = wave_max_small(top);
+    base_top = wave_max_small(base_top);
+    pt Q = ris_lincomb_sum(mine, lincomb_rw + tid, (int)block, (int)terms, top);
+    ring_release(ring, hold + wave_in_block);
+    if (kb) Q = base_mul_onto(Q, base, lincomb_rw + 9 * terms * block + wave_in_block * 64u + lane_id_fresh(), (int)block, base_top);
+    u64 w[4];
+    ris_lincomb_encode(w, Q, dec);
+    const u32 i_late = wave_first + lane_id_fresh();
+    if (i_late < n) {
+        store_words256(out + 32 * (size_t)i_late, w);
+        if (ok) ok[i_late] = dec ? 1 : 0;
+    }
+}
 
 // ---- fixed-base multiplication of the curve basepoint ------------------------
 // The reference's only fixed-base routine, window_naf_mul (edwards.rs:155-171), mis-indexes its
@@ -1150,70 +1226,13 @@ ZC_KERNEL_3W void k_ris_roundtrip_mul_fast(const uint8_t* in, const u64* k, uint
 // L2-resident) and k*B = sum_w sign(d_w) * T[w][|d_w| - 1] over the signed radix-256 digits --
 // 33 cached additions, no doublings (round 1 / first half of round 2: radix 16, 66 additions over a 66 KB table).  Equal to `&BASEPOINT * &k` as a group element; the fused
 // variant emits Ristretto encodings, which are bit-identical to the reference's.
-constexpr int ZC_BASE_WINDOWS = 33;                      // signed radix-256 digits of a 260-bit scalar (+ carry)
-constexpr int ZC_BASE_ENTRIES = 128;                     // |digit| = 1 .. 128
-
+// (ZC_BASE_WINDOWS, ZC_BASE_ENTRIES and the per-lane parts -- base_table_column, scalar_digits256, base_mul -- are in zc_curve.hip.h.)
 // lane j (0..127) builds the column (j+1) * 256^w * B for w = 0..32
 ZC_KERNEL void k_base_table_build(u32* table)
 {
     const int j = threadIdx.x;
     if (j >= ZC_BASE_ENTRIES) return;
-    pt B;
-    B.X = fe_const<FP>(ModP::BASE_X_M);
-    B.Y = fe_const<FP>(ModP::BASE_Y_M);
-    B.Z = fe_one_m<FP>();
-    B.T = fe_const<FP>(ModP::BASE_T_M);
-    pt P = B;
-    for (int a = 0; a < ZC_BASE_ENTRIES - 1; a++) {
-        const pt s = pt_add(P, B);
-        P = pt_select(a < j, s, P);                       // P = (j+1) * B
-    }
-    for (int w = 0; w < ZC_BASE_WINDOWS; w++) {
-        // entries are normalised to Z = 1 once, here, so every later addition against them is mixed
-        const fe zi = fp_invert(P.Z);
-        pt A;
-        A.X = fp_mul(P.X, zi);
-        A.Y = fp_mul(P.Y, zi);
-        A.Z = fe_one_m<FP>();
-        A.T = fp_mul(A.X, A.Y);
-        niels_store(table + 32 * (w * ZC_BASE_ENTRIES + j), niels_from_pt(A));
-#pragma unroll 1
-        for (int t = 0; t < 8; t++) P = pt_add(P, P);
-    }
-}
-// Signed radix-256 digits of the 260-bit scalar, d_i in [-128, 128), 33 digits (carry included), stored as
-// bytes at dig[i * stride]; returns the index of the highest non-zero digit or -1.
-ZC_DI int scalar_digits256(int8_t* __restrict__ dig, int stride, const u64 (&l)[5])
-{
-    u32 w[9];
-    int nb;
-    {
-        u32 tmp[9];
-        scalar_to_words(tmp, 1, l, nb);
-#pragma unroll
-        for (int k = 0; k < 9; k++) w[k] = tmp[k];
-    }
-    int carry = 0, top = -1;
-    for (int i = 0; i < ZC_BASE_WINDOWS; i++) {
-        int d = (int)((w[i >> 2] >> ((i & 3) * 8)) & 255u) + carry;
-        carry = d >= 128;
-        d -= carry << 8;
-        dig[i * stride] = (int8_t)d;
-        if (d != 0) top = i;
-    }
-    return top;
-}
-ZC_DI pt base_mul(const u32* __restrict__ table, const int8_t* __restrict__ dig, int stride, int top)
-{
-    pt Q = pt_identity();
-    for (int w = top; w >= 0; w--) {
-        const int d = dig[w * stride];
-        const int mag = d < 0 ? -d : d;
-        niels c = niels_identity();
-        if (mag != 0) c = niels_load(table + 32 * (w * ZC_BASE_ENTRIES + mag - 1));
-        Q = pt_add_cached<false, true>(Q, niels_cond_neg(d < 0, c));     // table entries and the identity have z = 1
-    }
-    return Q;
+    base_table_column(table, j);
 }
 ZC_KERNEL void k_ed_mul_base(const u64* k, u64* out, const u32* table, size_t n)
 {

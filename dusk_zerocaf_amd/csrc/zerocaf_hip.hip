@@ -1723,6 +1723,34 @@ int zc_ris_mul_base_compress(zc_ctx* ctx, const uint64_t* k, uint8_t* out32, siz
     });
     return rc ? rc : inner;
 }
+// out32[i] = compress(base_scalars[i] * B + sum_j scalars[i][j] * decompress(in32[i][j])): zc_ed_lincomb's windowed core between
+// the two codecs, the basepoint term from the comb table (zc_kernels.hip.h: k_ris_lincomb)
+int zc_ris_lincomb(zc_ctx* ctx, const uint8_t* in32, const uint64_t* scalars, size_t terms, const uint64_t* base_scalars, uint8_t* out32,
+                   uint8_t* ok, size_t n)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    REQUIRE(in32); REQUIRE(scalars); REQUIRE(out32);
+    const size_t slots_used = terms + (base_scalars ? 1 : 0);             // the base term takes one of the scalar slots
+    if (terms < 1 || terms > ZC_LINCOMB_MAX_TERMS || slots_used > ZC_LINCOMB_MAX_TERMS)
+        return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb: terms must be at least 1, terms + (base_scalars != NULL) at most ZC_LINCOMB_MAX_TERMS");
+    if (n >= ((size_t)1 << 31) / terms + (((size_t)1 << 31) % terms != 0)) return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb: n * terms must stay below 2^31");
+    Arg args[5] = {in_arg(in32, 32 * terms), in_arg(scalars, 40 * terms), in_arg(base_scalars, 40), out_arg(out32, 32), out_arg(ok, 1)};
+    int inner = ZC_OK;
+    int rc = run_batched(ctx, args, 5, n, [&](void** d, size_t cnt, DevState& D) {
+        const zc::u32* comb = nullptr;
+        if (d[2] && (inner = base_table(D, &comb)) != ZC_OK) return;
+        // as zc_ed_lincomb: 128-lane workgroups from five scalar slots on (36 bytes of LDS per lane and slot)
+        const unsigned block = slots_used > 4 ? 128u : (unsigned)zc::ZC_BLOCK;
+        const zc::u32 units = (zc::u32)ring_units_per_xcd(terms);
+        inner = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ris_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * slots_used * block, D.s(),
+                               (const uint8_t*)d[0] + 32 * terms * off, (const u64*)d[1] + 5 * terms * off, (zc::u32)terms,
+                               d[2] ? (const u64*)d[2] + 5 * off : (const u64*)nullptr, (uint8_t*)d[3] + 32 * off,
+                               d[4] ? (uint8_t*)d[4] + off : (uint8_t*)nullptr, comb, table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
+        }, terms);
+    }, true);
+    return rc ? rc : inner;
+}
 
 // window_naf_mul (src/edwards.rs:155-171) with its table indexed correctly: see k_ed_mul_base_wnaf
 int zc_ed_mul_base_wnaf(zc_ctx* ctx, const uint64_t* k, unsigned width, uint64_t* out, size_t n)

@@ -374,6 +374,35 @@ class Engine:
         self._call("zc_ris_roundtrip_mul", pb, pk, po, pko, n)
         return out, ok
 
+    def ris_lincomb(self, enc, scalars, base_scalars=None):
+        """out32[i] = compress(base_scalars[i] * B + sum_j scalars[i, j] * decompress(enc[i, j])) (zc_ris_lincomb): (n, t, 32)
+        uint8 encodings, (n, t, 5) scalars and, for the basepoint term, (n, 5) base scalars, t + (base term) <= 8 -- numpy
+        arrays, or contiguous torch tensors on one device (the call then runs on torch's current stream and the results stay
+        on the device) -> ((n, 32) uint8, (n,) uint8 accept mask) of the same kind.  The bytes are those of the reference's
+        decompress / Mul<Scalar> / + / compress; a row with an undecodable term is 32 zero bytes with ok = 0."""
+        given = [enc, scalars] + ([] if base_scalars is None else [base_scalars])
+        tensors = _is_torch(enc)
+        assert all(_is_torch(x) == tensors for x in given), "ris_lincomb: the arrays must all be numpy arrays or all torch tensors"
+        if not tensors:
+            enc, scalars = np.ascontiguousarray(enc, dtype=np.uint8), np.ascontiguousarray(scalars, dtype=np.uint64)
+            if base_scalars is not None:
+                base_scalars = np.ascontiguousarray(base_scalars, dtype=np.uint64)
+        assert enc.ndim == 3 and scalars.ndim == 3 and enc.shape[2] == 32 and scalars.shape[2] == 5, (enc.shape, scalars.shape)
+        assert tuple(enc.shape[:2]) == tuple(scalars.shape[:2]), (enc.shape, scalars.shape)
+        n, t = int(enc.shape[0]), int(enc.shape[1])
+        assert base_scalars is None or tuple(base_scalars.shape) == (n, 5), base_scalars.shape
+        if tensors:
+            assert enc.is_contiguous() and enc.element_size() == 1 and scalars.is_contiguous() and scalars.element_size() == 8
+            assert base_scalars is None or (base_scalars.is_contiguous() and base_scalars.element_size() == 8)
+            self._follow_torch_stream(enc)
+            pe, pk, pb = enc.data_ptr(), scalars.data_ptr(), None if base_scalars is None else base_scalars.data_ptr()
+        else:
+            pe, pk, pb = enc.ctypes.data, scalars.ctypes.data, None if base_scalars is None else base_scalars.ctypes.data
+        out, po = self._alloc(enc, n, 32, np.uint8)
+        ok, pko = self._alloc(enc, n, 0, np.uint8)
+        self._call("zc_ris_lincomb", pe, pk, t, pb, po, pko, n)
+        return out, ok
+
     # ------------------------------------------------------------------ next rows (N3, N4)
     def _flag(self, name, p):
         p, pp, n = self._prep(p, 20, np.uint64)

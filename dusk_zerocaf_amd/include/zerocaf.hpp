@@ -22,6 +22,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/zerocaf_hip.h"
@@ -678,6 +679,31 @@ inline std::vector<EdwardsPoint> ed_lincomb(const std::vector<std::vector<Edward
     std::vector<EdwardsPoint> out(n);
     for (size_t i = 0; i < n; i++) out[i] = EdwardsPoint::unflat(&o[20 * i]);
     return out;
+}
+// Wire-format linear combinations, one per row (zc_ris_lincomb): compress(bs[i] * RISTRETTO_BASEPOINT + sum_j kss[i][j] *
+// decompress(ess[i][j])), bit-identical to the reference's composition; 1..8 terms of one count for every row, 1..7 with a
+// base term (bs empty: none).  first: the encodings (32 zero bytes where a term did not decode), second: the accept mask.
+inline std::pair<std::vector<CompressedRistretto>, std::vector<uint8_t>> ris_lincomb(const std::vector<std::vector<CompressedRistretto>>& ess,
+                                                                                     const std::vector<std::vector<Scalar>>& kss,
+                                                                                     const std::vector<Scalar>& bs = {})
+{
+    if (ess.size() != kss.size() || (!bs.empty() && bs.size() != ess.size())) throw std::invalid_argument("ris_lincomb: size mismatch");
+    const size_t n = ess.size(), t = n ? ess[0].size() : 1;
+    std::vector<uint8_t> e(n * t * 32), o(n * 32), ok(n);
+    std::vector<uint64_t> k(n * t * 5), b(bs.size() * 5);
+    for (size_t i = 0; i < n; i++) {
+        if (ess[i].size() != t || kss[i].size() != t) throw std::invalid_argument("ris_lincomb: rows of different lengths");
+        for (size_t j = 0; j < t; j++) {
+            std::memcpy(&e[32 * (i * t + j)], ess[i][j].bytes.data(), 32);
+            std::memcpy(&k[5 * (i * t + j)], kss[i][j].l.data(), 40);
+        }
+        if (!bs.empty()) std::memcpy(&b[5 * i], bs[i].l.data(), 40);
+    }
+    std::vector<CompressedRistretto> out(n);
+    if (n == 0) return {out, ok};
+    Backend::check(zc_ris_lincomb(Backend::ctx(), e.data(), k.data(), t, bs.empty() ? nullptr : b.data(), o.data(), ok.data(), n), "zc_ris_lincomb");
+    for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
+    return {out, ok};
 }
 // {regime (0 = scalar multiplications + folds, 1 = buckets), c, W, affine, run length, segment buckets, sort passes, record
 // stride bytes} of a batch of `batch` instances of n pairs

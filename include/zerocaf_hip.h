@@ -327,6 +327,26 @@ int zc_msm_batch_plan(zc_ctx *ctx, size_t n, size_t batch, int points_aligned16,
 #define ZC_LINCOMB_MAX_TERMS 8
 int zc_ed_lincomb(zc_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t terms, uint64_t *out, size_t n);
 
+/* ---- wire-format linear combinations (additive to ABI 0.6): the verification equation R ?= s*B - c*A in one call -------- */
+/* out32[i] = compress(base_scalars[i] * RISTRETTO_BASEPOINT + sum_{j < terms} scalars[i][j] * decompress(in32[i][j]))
+ * with the reference's decompress (src/ristretto.rs:96-154), Mul<Scalar>, + and compress (:398-425); the 32 bytes are
+ * bit-identical to that composition (an encoding depends only on the group element, as for zc_ris_roundtrip_mul).
+ * in32: n x terms x 32 bytes, row-major (row i owns `terms` consecutive encodings); scalars: n x terms x 5 limbs;
+ * base_scalars: NULL (no basepoint term) or n x 5 limbs; out32: n x 32 bytes; ok: NULL or n bytes.
+ * Every scalar, the base term's included, is a Mul<Scalar> operand (raw limbs, then the rule of double_and_add's loop test,
+ * as zc_ed_lincomb and zc_ed_mul_base read them).
+ * A row with an undecodable term: ok[i] = 0 and out32[i] = 32 zero bytes, whatever its scalars (a zero scalar on that term
+ * included: the reference returns None before it multiplies).  Otherwise ok[i] = 1; an identity sum is 32 zero bytes, ok = 1.
+ * terms >= 1 and terms + (base_scalars != NULL) <= ZC_LINCOMB_MAX_TERMS (the base term takes one of the eight scalar slots);
+ * n * terms < 2^31; else ZC_ERR_BAD_ARG before anything is touched.  n == 0: ZC_OK, nothing written.
+ * Every non-NULL array in HOST memory (staged in chunks, synchronous; a multi-device context shards the rows) or every one on
+ * one device of the context (in place, asynchronous on the context stream), else ZC_ERR_MIXED_MEM.
+ * Per row: one decode per term, 1827 + 567 terms field multiplications for the shared doubling chain, 33 mixed additions for
+ * the base term, one encode; no intermediate point reaches memory.  Shares the windowed core's table ring and its failure
+ * report (see zc_last_error above): a wave that gives up on its slot writes all-ones bytes and ok = 0.                      */
+int zc_ris_lincomb(zc_ctx *ctx, const uint8_t *in32, const uint64_t *scalars, size_t terms, const uint64_t *base_scalars,
+                   uint8_t *out32, uint8_t *ok, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

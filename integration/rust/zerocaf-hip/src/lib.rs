@@ -856,6 +856,36 @@ impl HipBackend {
         Ok(masked(enc, &ok))
     }
 
+    /// Wire-format linear combinations, one per row (`zc_ris_lincomb`): `(base[i] * RISTRETTO_BASEPOINT + sum_j ks[i][j] *
+    /// cs[i][j].decompress()?).compress()`, bit-identical to that composition; 1..8 terms of one count for every row, 1..7
+    /// with a base term.  `None` where a term of the row does not decode.
+    pub fn ris_lincomb(&self, cs: &[Vec<CompressedRistretto>], ks: &[Vec<Scalar>], base: Option<&[Scalar]>) -> Result<Vec<Option<CompressedRistretto>>> {
+        assert_eq!(cs.len(), ks.len());
+        let n = cs.len();
+        let t = cs.first().map_or(1, |c| c.len());
+        let mut flat: Vec<u8> = Vec::with_capacity(n * t * 32);
+        let mut fk = Vec::with_capacity(n * t * 5);
+        for (c, k) in cs.iter().zip(ks) {
+            assert!(c.len() == t && k.len() == t);
+            flat.extend(c.iter().flat_map(|e| e.0.iter().copied()));
+            fk.extend(flat_sc(k));
+        }
+        let fb = base.map(|b| {
+            assert_eq!(b.len(), n);
+            flat_sc(b)
+        });
+        if n == 0 {
+            return Ok(Vec::new());
+        }
+        let (mut out, mut ok) = (vec![0u8; n * 32], vec![0u8; n]);
+        let pb = fb.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
+        check(unsafe {
+            ffi::zc_ris_lincomb(self.ctx, flat.as_ptr(), fk.as_ptr(), t, pb, out.as_mut_ptr(), ok.as_mut_ptr(), n)
+        })?;
+        let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
+        Ok(masked(enc, &ok))
+    }
+
     /// `p.is_valid()` (`:205-222`).
     pub fn ris_is_valid(&self, p: &[RistrettoPoint]) -> Result<Vec<bool>> {
         Ok(flags(self.flag(ffi::zc_ris_is_valid, &flat_ris(p), p.len())?))

@@ -14,6 +14,8 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -85,6 +87,7 @@ struct Tuning {
     long test_stream_min = 0;        // ZC_TEST_STREAM_MIN_BYTES=b: the 40-byte element ops take their LDS-staged kernels from b bytes per call on
     bool test_ring_poison = false;   // ZC_TEST_RING_POISON: pretend a wave of every windowed-core launch gave up
     unsigned test_ring_spins = 0;    // ZC_TEST_RING_SPINS=b: waves give up after 2^b polls (default 22, about 4 s)
+    long test_launch_fail = 0;       // ZC_TEST_LAUNCH_FAIL=j: the j-th launch (1-based) of every device job of a batched call is refused (ZC_ERR_NOMEM)
 };
 // (the compile-time variants of the MSM pipeline: zc_msm.hip.h, ZC_MSM_* macros)
 inline long env_long(const char* name, long lo, long hi, long unset)
@@ -133,6 +136,7 @@ Tuning tuning_from_env()
     t.test_stream_min = env_long("ZC_TEST_STREAM_MIN_BYTES", 1, 1l << 40, 0);
     t.test_ring_poison = getenv("ZC_TEST_RING_POISON") != nullptr;
     t.test_ring_spins = (unsigned)env_long("ZC_TEST_RING_SPINS", 1, 30, 0);
+    t.test_launch_fail = env_long("ZC_TEST_LAUNCH_FAIL", 1, 1l << 40, 0);
 #endif
     return t;
 }
@@ -210,10 +214,10 @@ namespace {
 
 int ring_check(struct DevState& D);     // windowed-core table ring: error word of the last launches (defined with fast_ring)
 
-// One buffer argument of a batched call.
+// One buffer argument of a batched call, as run_batched moves it (built by `batched` below from the typed description).
 struct Arg {
     const void* ptr;     // caller pointer (host or device), may be null when optional
-    size_t elt_bytes;    // bytes per element
+    size_t elt_bytes;    // bytes per row
     bool is_out;
 };
 
@@ -276,13 +280,22 @@ inline size_t host_chunk_elems(size_t cnt, bool heavy, long forced)
     chunk = (chunk + 1023) / 1024 * 1024;
     return std::max(chunk, (cnt + MAX_CHUNKS - 1) / MAX_CHUNKS);
 }
-// Launch functor: receives device pointers in argument order, element count, device state.
+// Launch functor: receives device pointers in argument order, element count, device state; returns a status.  A launch that
+// fails ends its device job: no further chunk is started, the job's streams are drained and the status (with the message, also
+// from a worker thread) goes to the caller; the outputs are then unspecified.
 template <class Launch>
-int run_batched(zc_ctx* ctx, Arg* args, int nargs, size_t n, Launch&& launch, bool heavy = false)
+int run_batched(zc_ctx* ctx, const Arg* args, int nargs, size_t n, Launch&& launch, bool heavy)
 {
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    if (nargs > MAX_ARGS) return fail(ZC_ERR_BAD_ARG, "too many arguments");
     if (n == 0) return ZC_OK;
+    // `calls`: the launches of one device job so far (the test build refuses the ZC_TEST_LAUNCH_FAIL-th without making it)
+    auto launch_counted = [&](void** d, size_t cnt, DevState& D, long& calls) -> int {
+#ifdef ZC_TEST_HOOKS
+        if (++calls == D.tune.test_launch_fail) return fail(ZC_ERR_NOMEM, "test: launch refused");
+#endif
+        (void)calls;
+        return launch(d, cnt, D);
+    };
     std::lock_guard<std::mutex> lock(ctx->mu);
 
     int ndevptr = 0, nhostptr = 0, dev_of_ptrs = -1;
@@ -311,7 +324,8 @@ int run_batched(zc_ctx* ctx, Arg* args, int nargs, size_t n, Launch&& launch, bo
         HIP_TRY(hipSetDevice(ds->device));
         void* dptr[MAX_ARGS];
         for (int a = 0; a < nargs; a++) dptr[a] = const_cast<void*>(args[a].ptr);
-        launch(dptr, n, *ds);
+        long calls = 0;
+        if (int rc = launch_counted(dptr, n, *ds, calls)) return rc;
         HIP_TRY(hipGetLastError());
         return ZC_OK;
     }
@@ -331,6 +345,7 @@ int run_batched(zc_ctx* ctx, Arg* args, int nargs, size_t n, Launch&& launch, bo
         const size_t chunk = host_chunk_elems(total, heavy, ctx->devs[di].tune.host_chunks);
         const size_t nchunks = (total + chunk - 1) / chunk;
         DevState& ds = ctx->devs[di];
+        long calls = 0;
         auto body = [&]() -> int {
             if (int rc0 = ring_check(ds)) return rc0;       // an asynchronous failure of an earlier call surfaces here
             HIP_TRY(hipSetDevice(ds.device));
@@ -359,7 +374,7 @@ int run_batched(zc_ctx* ctx, Arg* args, int nargs, size_t n, Launch&& launch, bo
                 }
                 HIP_TRY(hipEventRecord(ds.ev[2 * j], ds.copy_in));
                 HIP_TRY(hipStreamWaitEvent(ds.s(), ds.ev[2 * j], 0));
-                launch(dptr, cnt, ds);
+                if (int lrc = launch_counted(dptr, cnt, ds, calls)) return lrc;
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(ds.ev[2 * j + 1], ds.s()));
                 return ZC_OK;
@@ -412,11 +427,50 @@ int run_batched(zc_ctx* ctx, Arg* args, int nargs, size_t n, Launch&& launch, bo
     return ZC_OK;
 }
 
-inline Arg in_arg(const void* p, size_t b) { return Arg{p, b, false}; }
-inline Arg out_arg(void* p, size_t b) { return Arg{p, b, true}; }
-
 #define REQUIRE(p) \
     if (!(p)) return fail(ZC_ERR_BAD_ARG, "null pointer: " #p)
+
+// One buffer of a batched call, described once: n rows of `per` elements of T.  Everything run_batched needs follows from the
+// type: a row is sizeof(T) * per bytes; rows of const T are inputs (uploaded), all others outputs (downloaded); the launch
+// gets the device pointer as T*.  `name` is the parameter's name in the message for a null pointer.
+template <class T>
+struct Rows {
+    T* ptr;              // the caller's pointer, host or device
+    size_t per;          // elements per row
+    const char* name;
+    bool optional;       // may be null: not staged, and the launch receives null
+};
+template <class T>
+inline Rows<T> rows(T* p, size_t per, const char* name, bool optional) { return Rows<T>{p, per, name, optional}; }
+#define ROWS(p, per) rows(p, per, #p, false)
+#define OPT_ROWS(p, per) rows(p, per, #p, true)
+
+template <class Launch, size_t... I, class... T>
+int batched_at(std::index_sequence<I...>, zc_ctx* ctx, size_t n, bool heavy, Launch& launch, const Rows<T>&... r)
+{
+    for (const char* missing : {(r.ptr || r.optional ? nullptr : r.name)...})
+        if (missing) return failf(ZC_ERR_BAD_ARG, "null pointer: %s", missing);
+    const Arg args[] = {Arg{r.ptr, sizeof(T) * r.per, !std::is_const<T>::value}...};
+    return run_batched(ctx, args, (int)sizeof...(T), n, [&](void** d, size_t cnt, DevState& D) -> int { return launch(D, cnt, static_cast<T*>(d[I])...); }, heavy);
+}
+// The batched call over the buffers r...: null checks (before anything else), then run_batched with
+// launch(D, cnt, device pointers typed as the buffers, in their order) -> status for every piece.  `heavy`: host_chunk_elems.
+template <class Launch, class... T>
+int batched(zc_ctx* ctx, size_t n, bool heavy, Launch&& launch, Rows<T>... r)
+{
+    static_assert(sizeof...(T) <= MAX_ARGS, "more buffers than a device slot has staging areas (MAX_ARGS)");
+    return batched_at(std::index_sequence_for<T...>{}, ctx, n, heavy, launch, r...);
+}
+// The launch of a kernel whose parameters are exactly the call's buffers followed by the count: one lane per row.
+template <class... A>
+auto plain(void (*k)(A...))
+{
+    return [k](DevState& D, size_t cnt, auto... p) -> int {
+        static_assert(std::is_same<void (*)(A...), void (*)(decltype(p)..., size_t)>::value, "the buffers are not the kernel's parameters");
+        hipLaunchKernelGGL(k, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt);
+        return ZC_OK;
+    };
+}
 
 typedef void (*kbin_t)(const u64*, const u64*, u64*, size_t);
 typedef void (*kun_t)(const u64*, u64*, size_t);
@@ -424,43 +478,48 @@ typedef void (*kun_t)(const u64*, u64*, size_t);
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Streams larger than this (bytes over all arrays of the call) use the LDS-staged kernel
-// `k_stream` when one is given: it wins only for the compute-free two-input ops beyond the
+// when one is given: it wins only for the compute-free two-input ops beyond the
 // 256 MB Infinity Cache (zc_kernels.hip.h, "LDS-staged element I/O").
 constexpr size_t STREAM_BYTES = (size_t)256 << 20;
 
-// `stream_min`: the call's bytes from which the staged kernel wins (STREAM_BYTES for the 40-byte element ops; the point ops
-// -- 160-byte records, far beyond what a lane reads well on its own -- from the first full launch on).
-// The test build can lower the 40-byte ops' threshold (ZC_TEST_STREAM_MIN_BYTES) so that small batches reach the staged kernels.
-inline size_t staged_min(const DevState& D, size_t elt, size_t stream_min)
+// The LDS-staged form of an element-wise kernel, taken when the call's arrays are all 16-byte aligned and hold more than
+// `min_bytes` together: STREAM_BYTES for the 40-byte element ops; the point ops -- 160-byte records, far beyond what a lane
+// reads well on its own -- from the first full launch on, with a workgroup size of their own.
+template <class K>
+struct Staged {
+    K kernel = nullptr;                  // null: the op has no staged form
+    size_t min_bytes = STREAM_BYTES;
+    unsigned block = zc::ZC_BLOCK;
+};
+// The test build can lower STREAM_BYTES itself (ZC_TEST_STREAM_MIN_BYTES) so that small batches reach the ops staged from there on.
+inline size_t staged_min(const DevState& D, size_t min_bytes)
 {
 #ifdef ZC_TEST_HOOKS
-    if (elt == 40 && D.tune.test_stream_min > 0) return (size_t)D.tune.test_stream_min;
+    if (min_bytes == STREAM_BYTES && D.tune.test_stream_min > 0) return (size_t)D.tune.test_stream_min;
 #endif
-    (void)D; (void)elt;
-    return stream_min;
+    (void)D;
+    return min_bytes;
 }
-int binop(zc_ctx* ctx, kbin_t k, kbin_t k_stream, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, size_t elt, size_t stream_min = STREAM_BYTES)
+// out = a op b / out = op a over rows of `per` limbs
+int binop(zc_ctx* ctx, kbin_t k, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, size_t per, Staged<kbin_t> st = {})
 {
-    REQUIRE(a); REQUIRE(b); REQUIRE(out);
-    // elt == 0: (point, scalar) -> point
-    Arg args[3] = {in_arg(a, elt ? elt : 160), in_arg(b, elt ? elt : 40), out_arg(out, elt ? elt : 160)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        const bool stream = k_stream && cnt * elt * 3 > staged_min(D, elt, stream_min) && aligned16(d[0]) && aligned16(d[1]) && aligned16(d[2]);
-        const unsigned blk = stream && elt == 160 ? (unsigned)zc::ED_STAGED_BLOCK : (unsigned)zc::ZC_BLOCK;     // the staged point kernels have their own workgroup size
-        D.staged_launches += stream ? 1 : 0;
-        hipLaunchKernelGGL(stream ? k_stream : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (u64*)d[2], cnt);
-    }, elt == 0);
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, const u64* db, u64* dout) {
+        const bool staged = st.kernel && cnt * sizeof(u64) * per * 3 > staged_min(D, st.min_bytes) && aligned16(da) && aligned16(db) && aligned16(dout);
+        const unsigned blk = staged ? st.block : (unsigned)zc::ZC_BLOCK;
+        D.staged_launches += staged ? 1 : 0;
+        hipLaunchKernelGGL(staged ? st.kernel : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), da, db, dout, cnt);
+        return ZC_OK;
+    }, ROWS(a, per), ROWS(b, per), ROWS(out, per));
 }
-int unop(zc_ctx* ctx, kun_t k, const uint64_t* a, uint64_t* out, size_t n, size_t elt, kun_t k_stream = nullptr, size_t stream_min = STREAM_BYTES)
+int unop(zc_ctx* ctx, kun_t k, const uint64_t* a, uint64_t* out, size_t n, size_t per, Staged<kun_t> st = {})
 {
-    REQUIRE(a); REQUIRE(out);
-    Arg args[2] = {in_arg(a, elt), out_arg(out, elt)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        const bool stream = k_stream && cnt * elt * 2 > staged_min(D, elt, stream_min) && aligned16(d[0]) && aligned16(d[1]);
-        const unsigned blk = stream && elt == 160 ? (unsigned)zc::ED_STAGED_BLOCK : (unsigned)zc::ZC_BLOCK;
-        D.staged_launches += stream ? 1 : 0;
-        hipLaunchKernelGGL(stream ? k_stream : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), (const u64*)d[0], (u64*)d[1], cnt);
-    });
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) {
+        const bool staged = st.kernel && cnt * sizeof(u64) * per * 2 > staged_min(D, st.min_bytes) && aligned16(da) && aligned16(dout);
+        const unsigned blk = staged ? st.block : (unsigned)zc::ZC_BLOCK;
+        D.staged_launches += staged ? 1 : 0;
+        hipLaunchKernelGGL(staged ? st.kernel : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), da, dout, cnt);
+        return ZC_OK;
+    }, ROWS(a, per), ROWS(out, per));
 }
 
 // Cost-sorted permutation for the unified-step kernels (see zc_kernels.hip.h "lane balancing").
@@ -596,22 +655,20 @@ void scalar_mul_on_device(DevState& D, const u64* p, const u64* k, u64* out, siz
 }
 int scalar_mul_impl(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t* out, size_t n)
 {
-    REQUIRE(p); REQUIRE(k); REQUIRE(out);
-    Arg args[3] = {in_arg(p, 160), in_arg(k, 40), out_arg(out, 160)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        scalar_mul_on_device(D, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], cnt);
-    }, true);
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, const u64* dk, u64* dout) {
+        scalar_mul_on_device(D, dp, dk, dout, cnt);
+        return ZC_OK;
+    }, ROWS(p, 20), ROWS(k, 5), ROWS(out, 20));
 }
 // the same scalar for every point, handed to the kernel by value
 int scalar_mul_bcast(zc_ctx* ctx, const uint64_t* p, const uint64_t (&k)[5], uint64_t* out, size_t n)
 {
-    REQUIRE(p); REQUIRE(out);
     zc::scalar_arg ka;
     for (int j = 0; j < 5; j++) ka.l[j] = k[j];
-    Arg args[2] = {in_arg(p, 160), out_arg(out, 160)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ed_scalar_mul_bcast, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], ka, (u64*)d[1], cnt);
-    }, true);
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, u64* dout) {
+        hipLaunchKernelGGL(zc::k_ed_scalar_mul_bcast, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dp, ka, dout, cnt);
+        return ZC_OK;
+    }, ROWS(p, 20), ROWS(out, 20));
 }
 
 // ---------------------------------------------------------------- MSM device pipeline
@@ -1116,6 +1173,32 @@ int msm_batch_on_device(DevState& D, const u64* dP, const u64* dK, size_t n, siz
     return ZC_OK;
 }
 
+// Montgomery's trick shares one inversion among the c consecutive elements of a lane (3 multiplications per
+// element + one inversion per lane).  c = cnt / INV_LANES_TARGET keeps that many lanes busy, capped at 64;
+// below 2 the kernels take one element per lane.  ZC_INV_CHUNK=c overrides (tuning, tests).
+constexpr size_t INV_LANES_TARGET = 65536;
+inline size_t inv_chunk(size_t cnt, const Tuning& tune)
+{
+    if (tune.inv_chunk) return (size_t)tune.inv_chunk;
+    size_t c = cnt / INV_LANES_TARGET;
+    return c > 32 ? 32 : c;
+}
+// The launch of an op with one inversion per element over the buffers p...: `k` (one element per lane) for a tiny batch or when
+// the output aliases an input, otherwise the chunked kernel -- `k_lone`, the independent-chain multiplier, when the lanes leave
+// at most one wave per SIMD (2^20 elements: BASELINE configs[1], -7 %).
+template <class K, class KC, class... P>
+int launch_shared_inversions(DevState& D, size_t cnt, bool in_place, K k, KC k_chunked, KC k_lone, P... p)
+{
+    const size_t c = inv_chunk(cnt, D.tune);
+    if (c < 2 || in_place) {
+        hipLaunchKernelGGL(k, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt);
+    } else {
+        const size_t lanes = (cnt + c - 1) / c;
+        hipLaunchKernelGGL(lanes <= (size_t)D.cus * 256 ? k_lone : k_chunked, dim3(grid_for(lanes)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt, (int)c);
+    }
+    return ZC_OK;
+}
+
 const uint64_t IDENT_POINT[20] = {0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 }  // namespace
@@ -1293,8 +1376,8 @@ int zc_ctx_synchronize(zc_ctx* ctx)
 }
 
 // ---- FieldElement
-int zc_fe_add(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_add, zc::k_fe_add_stream, a, b, o, n, 40); }
-int zc_fe_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_sub, zc::k_fe_sub_stream, a, b, o, n, 40); }
+int zc_fe_add(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_add, a, b, o, n, 5, {zc::k_fe_add_stream}); }
+int zc_fe_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_sub, a, b, o, n, 5, {zc::k_fe_sub_stream}); }
 // Mul / Square: LDS-staged beyond the Infinity Cache since round 5 -- with the one-pass product (151 / 115 multiply-adds instead of
 // 270 / 234) the staged kernels' coalesced traffic pays: 2^24 elements, same box, mul 0.411 -> 0.376 ms, square 0.273 -> 0.248
 // (with the two Montgomery passes of rounds 1-4 the staged kernels were the slower ones: 0.435 against 0.360 ms).
@@ -1309,209 +1392,134 @@ int zc_fe_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size
 #ifndef ZC_NEG_STAGED
 #define ZC_NEG_STAGED 1
 #endif
-int zc_fe_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_mul, ZC_MULSQ_STAGED ? zc::k_fe_mul_stream : nullptr, a, b, o, n, 40, ZC_MULSQ_STAGED_MIN_BYTES); }
-int zc_fe_neg(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_neg, a, o, n, 40, ZC_NEG_STAGED ? zc::k_fe_neg_stream : nullptr); }
-int zc_fe_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_square, a, o, n, 40, ZC_MULSQ_STAGED ? zc::k_fe_square_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES); }
-
-// Montgomery's trick shares one inversion among the c consecutive elements of a lane (3 multiplications per
-// element + one inversion per lane).  c = cnt / INV_LANES_TARGET keeps that many lanes busy, capped at 64;
-// below 2 the kernels take one element per lane.  ZC_INV_CHUNK=c overrides (tuning, tests).
-constexpr size_t INV_LANES_TARGET = 65536;
-inline size_t inv_chunk(size_t cnt, const Tuning& tune)
-{
-    if (tune.inv_chunk) return (size_t)tune.inv_chunk;
-    size_t c = cnt / INV_LANES_TARGET;
-    return c > 32 ? 32 : c;
-}
+int zc_fe_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_mul, a, b, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_fe_mul_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
+int zc_fe_neg(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_neg, a, o, n, 5, {ZC_NEG_STAGED ? zc::k_fe_neg_stream : nullptr}); }
+int zc_fe_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_square, a, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_fe_square_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
 
 int zc_fe_invert(zc_ctx* ctx, const uint64_t* a, uint64_t* out, uint8_t* ok, size_t n)
 {
-    REQUIRE(a); REQUIRE(out);
-    Arg args[3] = {in_arg(a, 40), out_arg(out, 40), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        const size_t c = inv_chunk(cnt, D.tune);
-        if (c < 2 || d[0] == d[1]) {                       // tiny batch or in-place: one element per lane
-            hipLaunchKernelGGL(zc::k_fe_invert, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt);
-        } else {
-            const size_t lanes = (cnt + c - 1) / c;
-            // at most one wave per SIMD (2^20 elements: BASELINE configs[1]): the independent-chain multiplier, -7 %
-            hipLaunchKernelGGL(lanes <= (size_t)D.cus * 256 ? zc::k_fe_invert_chunked_lone : zc::k_fe_invert_chunked, dim3(grid_for(lanes)), dim3(zc::ZC_BLOCK), 0, D.s(),
-                               (const u64*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt, (int)c);
-        }
-    });
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* da, u64* dout, uint8_t* dok) {
+        return launch_shared_inversions(D, cnt, dout == da, zc::k_fe_invert, zc::k_fe_invert_chunked, zc::k_fe_invert_chunked_lone, da, dout, dok);
+    }, ROWS(a, 5), ROWS(out, 5), OPT_ROWS(ok, 1));
 }
 int zc_fe_div(zc_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t* out, uint8_t* ok, size_t n)
 {
-    REQUIRE(a); REQUIRE(b); REQUIRE(out);
-    Arg args[4] = {in_arg(a, 40), in_arg(b, 40), out_arg(out, 40), out_arg(ok, 1)};
-    return run_batched(ctx, args, 4, n, [&](void** d, size_t cnt, DevState& D) {
-        const size_t c = inv_chunk(cnt, D.tune);
-        if (c < 2 || d[2] == d[0] || d[2] == d[1]) {
-            hipLaunchKernelGGL(zc::k_fe_div, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (u64*)d[2], (uint8_t*)d[3], cnt);
-        } else {
-            const size_t lanes = (cnt + c - 1) / c;
-            hipLaunchKernelGGL(lanes <= (size_t)D.cus * 256 ? zc::k_fe_div_chunked_lone : zc::k_fe_div_chunked, dim3(grid_for(lanes)), dim3(zc::ZC_BLOCK), 0, D.s(),
-                               (const u64*)d[0], (const u64*)d[1], (u64*)d[2], (uint8_t*)d[3], cnt, (int)c);
-        }
-    });
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* da, const u64* db, u64* dout, uint8_t* dok) {
+        return launch_shared_inversions(D, cnt, dout == da || dout == db, zc::k_fe_div, zc::k_fe_div_chunked, zc::k_fe_div_chunked_lone, da, db, dout, dok);
+    }, ROWS(a, 5), ROWS(b, 5), ROWS(out, 5), OPT_ROWS(ok, 1));
 }
-int zc_fe_half(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_half, a, o, n, 40); }
-int zc_fe_pow(zc_ctx* c, const uint64_t* a, const uint64_t* e, uint64_t* o, size_t n) { return binop(c, zc::k_fe_pow, nullptr, a, e, o, n, 40); }
-static int fe_flag_op(zc_ctx* ctx, void (*k)(const u64*, uint8_t*, size_t), const uint64_t* a, uint8_t* out, size_t n)
-{
-    REQUIRE(a); REQUIRE(out);
-    Arg args[2] = {in_arg(a, 40), out_arg(out, 1)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(k, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
+int zc_fe_half(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_half, a, o, n, 5); }
+int zc_fe_pow(zc_ctx* c, const uint64_t* a, const uint64_t* e, uint64_t* o, size_t n) { return binop(c, zc::k_fe_pow, a, e, o, n, 5); }
 // ZC_JACOBI_ROUNDS=r (tests): rounds of 30 positive division steps before a lane falls back to the exponentiation
 int zc_fe_legendre_symbol(zc_ctx* ctx, const uint64_t* a, uint8_t* out, size_t n)
 {
-    REQUIRE(a); REQUIRE(out);
-    Arg args[2] = {in_arg(a, 40), out_arg(out, 1)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_fe_legendre, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt, D.tune.jacobi_rounds >= 0 ? D.tune.jacobi_rounds : zc::JACOBI_MAX_ROUNDS);
-    });
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* da, uint8_t* dout) {
+        hipLaunchKernelGGL(zc::k_fe_legendre, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), da, dout, cnt, D.tune.jacobi_rounds >= 0 ? D.tune.jacobi_rounds : zc::JACOBI_MAX_ROUNDS);
+        return ZC_OK;
+    }, ROWS(a, 5), ROWS(out, 1));
 }
-int zc_fe_is_positive(zc_ctx* c, const uint64_t* a, uint8_t* o, size_t n) { return fe_flag_op(c, zc::k_fe_is_positive, a, o, n); }
+int zc_fe_is_positive(zc_ctx* ctx, const uint64_t* a, uint8_t* out, size_t n) { return batched(ctx, n, false, plain(zc::k_fe_is_positive), ROWS(a, 5), ROWS(out, 1)); }
 int zc_fe_mod_sqrt(zc_ctx* ctx, const uint64_t* a, int sign, uint64_t* out, uint8_t* ok, size_t n)
 {
-    REQUIRE(a); REQUIRE(out);
-    Arg args[3] = {in_arg(a, 40), out_arg(out, 40), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_fe_mod_sqrt, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], sign, (u64*)d[1], (uint8_t*)d[2], cnt);
-    });
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout, uint8_t* dok) {
+        hipLaunchKernelGGL(zc::k_fe_mod_sqrt, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), da, sign, dout, dok, cnt);
+        return ZC_OK;
+    }, ROWS(a, 5), ROWS(out, 5), OPT_ROWS(ok, 1));
 }
-int zc_fe_from_bytes(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, size_t n)
+// k_from_bytes serves both codecs: the field's takes every 32 bytes (no mask), the scalar's rejects what is not below the order
+static int from_bytes(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* ok, int is_scalar, size_t n)
 {
-    REQUIRE(in32); REQUIRE(out);
-    Arg args[2] = {in_arg(in32, 32), out_arg(out, 40)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_from_bytes, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0], (u64*)d[1], (uint8_t*)nullptr, 0, cnt);
-    });
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const uint8_t* din, u64* dout, uint8_t* dok) {
+        hipLaunchKernelGGL(zc::k_from_bytes, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), din, dout, dok, is_scalar, cnt);
+        return ZC_OK;
+    }, ROWS(in32, 32), ROWS(out, 5), OPT_ROWS(ok, 1));
 }
-int zc_fe_to_bytes(zc_ctx* ctx, const uint64_t* in, uint8_t* out32, size_t n)
-{
-    REQUIRE(in); REQUIRE(out32);
-    Arg args[2] = {in_arg(in, 40), out_arg(out32, 32)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_to_bytes, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
+int zc_fe_from_bytes(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, size_t n) { return from_bytes(ctx, in32, out, nullptr, 0, n); }
+int zc_fe_to_bytes(zc_ctx* ctx, const uint64_t* in, uint8_t* out32, size_t n) { return batched(ctx, n, false, plain(zc::k_to_bytes), ROWS(in, 5), ROWS(out32, 32)); }
 int zc_fe_sqrt_ratio_i(zc_ctx* ctx, const uint64_t* u, const uint64_t* v, uint64_t* out, uint8_t* was_square, size_t n)
 {
-    REQUIRE(u); REQUIRE(v); REQUIRE(out);
-    Arg args[4] = {in_arg(u, 40), in_arg(v, 40), out_arg(out, 40), out_arg(was_square, 1)};
-    return run_batched(ctx, args, 4, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_fe_sqrt_ratio_i, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (u64*)d[2], (uint8_t*)d[3], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_fe_sqrt_ratio_i), ROWS(u, 5), ROWS(v, 5), ROWS(out, 5), OPT_ROWS(was_square, 1));
 }
 int zc_fe_inv_sqrt(zc_ctx* ctx, const uint64_t* a, uint64_t* out, uint8_t* was_square, size_t n)
 {
-    REQUIRE(a); REQUIRE(out);
-    Arg args[3] = {in_arg(a, 40), out_arg(out, 40), out_arg(was_square, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_fe_inv_sqrt, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_fe_inv_sqrt), ROWS(a, 5), ROWS(out, 5), OPT_ROWS(was_square, 1));
 }
 
 // ---- Scalar
-int zc_sc_add(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_add, zc::k_sc_add_stream, a, b, o, n, 40); }
-int zc_sc_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_sub, zc::k_sc_sub_stream, a, b, o, n, 40); }
-int zc_sc_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_mul, ZC_MULSQ_STAGED ? zc::k_sc_mul_stream : nullptr, a, b, o, n, 40, ZC_MULSQ_STAGED_MIN_BYTES); }
-int zc_sc_neg(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_neg, a, o, n, 40, ZC_NEG_STAGED ? zc::k_sc_neg_stream : nullptr); }
-int zc_sc_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_square, a, o, n, 40, ZC_MULSQ_STAGED ? zc::k_sc_square_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES); }
+int zc_sc_add(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_add, a, b, o, n, 5, {zc::k_sc_add_stream}); }
+int zc_sc_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_sub, a, b, o, n, 5, {zc::k_sc_sub_stream}); }
+int zc_sc_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_mul, a, b, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_sc_mul_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
+int zc_sc_neg(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_neg, a, o, n, 5, {ZC_NEG_STAGED ? zc::k_sc_neg_stream : nullptr}); }
+int zc_sc_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_square, a, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_sc_square_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
 // S-x rows: the Scalar operations beside the default scalar-mul path
-int zc_sc_half(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_half, a, o, n, 40); }
-int zc_sc_pow(zc_ctx* c, const uint64_t* a, const uint64_t* e, uint64_t* o, size_t n) { return binop(c, zc::k_sc_pow, nullptr, a, e, o, n, 40); }
+int zc_sc_half(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_half, a, o, n, 5); }
+int zc_sc_pow(zc_ctx* c, const uint64_t* a, const uint64_t* e, uint64_t* o, size_t n) { return binop(c, zc::k_sc_pow, a, e, o, n, 5); }
 int zc_sc_shr(zc_ctx* ctx, const uint64_t* a, unsigned shift, uint64_t* out, size_t n)
 {
-    REQUIRE(a); REQUIRE(out);
     if (shift > 255) return fail(ZC_ERR_BAD_ARG, "zc_sc_shr: the reference shifts by a u8");
-    Arg args[2] = {in_arg(a, 40), out_arg(out, 40)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_sc_shr, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (zc::u32)shift, (u64*)d[1], cnt);
-    });
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) {
+        hipLaunchKernelGGL(zc::k_sc_shr, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), da, (zc::u32)shift, dout, cnt);
+        return ZC_OK;
+    }, ROWS(a, 5), ROWS(out, 5));
 }
-int zc_sc_into_bits(zc_ctx* ctx, const uint64_t* a, uint8_t* bits256, size_t n)
-{
-    REQUIRE(a); REQUIRE(bits256);
-    Arg args[2] = {in_arg(a, 40), out_arg(bits256, 256)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_sc_into_bits, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
+int zc_sc_into_bits(zc_ctx* ctx, const uint64_t* a, uint8_t* bits256, size_t n) { return batched(ctx, n, false, plain(zc::k_sc_into_bits), ROWS(a, 5), ROWS(bits256, 256)); }
 int zc_sc_compute_naf(zc_ctx* ctx, const uint64_t* a, unsigned width, int8_t* naf256, size_t n)
 {
-    REQUIRE(a); REQUIRE(naf256);
     if (width == 1 || width > 7) return fail(ZC_ERR_BAD_ARG, "zc_sc_compute_naf: width 0 (compute_NAF) or 2..7 (compute_window_NAF: digits are i8)");
-    Arg args[2] = {in_arg(a, 40), out_arg(naf256, 256)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_sc_compute_naf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (zc::u32)width, (int8_t*)d[1], cnt);
-    });
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, int8_t* dnaf) {
+        hipLaunchKernelGGL(zc::k_sc_compute_naf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), da, (zc::u32)width, dnaf, cnt);
+        return ZC_OK;
+    }, ROWS(a, 5), ROWS(naf256, 256));
 }
-int zc_sc_from_bytes(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* ok, size_t n)
-{
-    REQUIRE(in32); REQUIRE(out);
-    Arg args[3] = {in_arg(in32, 32), out_arg(out, 40), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_from_bytes, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0], (u64*)d[1], (uint8_t*)d[2], 1, cnt);
-    });
-}
+int zc_sc_from_bytes(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* ok, size_t n) { return from_bytes(ctx, in32, out, ok, 1, n); }
 int zc_sc_to_bytes(zc_ctx* ctx, const uint64_t* in, uint8_t* out32, size_t n) { return zc_fe_to_bytes(ctx, in, out32, n); }
 
 // ---- EdwardsPoint
 // staged records from 2^12 points on (below, a launch is a handful of workgroups and the barriers only cost)
 constexpr size_t ED_STAGED_MIN_BYTES = (size_t)160 * 3 << 12;     // binop compares cnt * 160 * 3 against it: above 2^12 points
 constexpr size_t ED_STAGED_MIN_BYTES_1 = (size_t)160 * 2 << 12;   // unop compares cnt * 160 * 2: the same 2^12 points for double / neg
-int zc_ed_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_add, zc::k_ed_add_staged, p, q, o, n, 160, ED_STAGED_MIN_BYTES); }
-int zc_ed_sub(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_sub, zc::k_ed_sub_staged, p, q, o, n, 160, ED_STAGED_MIN_BYTES); }
-int zc_ed_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_double, p, o, n, 160, zc::k_ed_double_staged, ED_STAGED_MIN_BYTES_1); }
-int zc_ed_neg(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_neg, p, o, n, 160, zc::k_ed_neg_staged, ED_STAGED_MIN_BYTES_1); }
+int zc_ed_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_add, p, q, o, n, 20, {zc::k_ed_add_staged, ED_STAGED_MIN_BYTES, zc::ED_STAGED_BLOCK}); }
+int zc_ed_sub(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_sub, p, q, o, n, 20, {zc::k_ed_sub_staged, ED_STAGED_MIN_BYTES, zc::ED_STAGED_BLOCK}); }
+int zc_ed_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_double, p, o, n, 20, {zc::k_ed_double_staged, ED_STAGED_MIN_BYTES_1, zc::ED_STAGED_BLOCK}); }
+int zc_ed_neg(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_neg, p, o, n, 20, {zc::k_ed_neg_staged, ED_STAGED_MIN_BYTES_1, zc::ED_STAGED_BLOCK}); }
 
+// the reference's other scalar multiplications, one lane per row: (point, scalar) -> point, a long-running kernel
+static int scalar_mul_variant(zc_ctx* ctx, kbin_t k, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n)
+{
+    return batched(ctx, n, true, plain(k), ROWS(a, 20), ROWS(b, 5), ROWS(out, 20));
+}
 int zc_ed_scalar_mul(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t* out, size_t n, unsigned flags)
 {
     if (flags == ZC_SCALAR_MUL_STRICT) return scalar_mul_impl(ctx, p, k, out, n);
-    if (flags == ZC_SCALAR_MUL_FAST) {
-        REQUIRE(p); REQUIRE(k); REQUIRE(out);
-        Arg args[3] = {in_arg(p, 160), in_arg(k, 40), out_arg(out, 160)};
-        int inner = ZC_OK;
-        int rc = run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-            inner = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
-                hipLaunchKernelGGL(zc::k_ed_scalar_mul_fast, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0] + 20 * off,
-                                   (const u64*)d[1] + 5 * off, (zc::u32)5, (u64*)d[2] + 20 * off, table, ring, slots, (zc::u32)c);
+    if (flags == ZC_SCALAR_MUL_FAST)
+        return batched(ctx, n, true, [](DevState& D, size_t cnt, const u64* dp, const u64* dk, u64* dout) {
+            return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+                hipLaunchKernelGGL(zc::k_ed_scalar_mul_fast, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), dp + 20 * off, dk + 5 * off, (zc::u32)5, dout + 20 * off,
+                                   table, ring, slots, (zc::u32)c);
             });
-        }, true);
-        return rc ? rc : inner;
-    }
-    if (flags == ZC_SCALAR_MUL_LTR_BIN) return binop(ctx, zc::k_ed_scalar_mul_ltr_bin, nullptr, p, k, out, n, 0);
-    if (flags == ZC_SCALAR_MUL_BINARY_NAF) return binop(ctx, zc::k_ed_scalar_mul_naf, nullptr, p, k, out, n, 0);
+        }, ROWS(p, 20), ROWS(k, 5), ROWS(out, 20));
+    if (flags == ZC_SCALAR_MUL_LTR_BIN) return scalar_mul_variant(ctx, zc::k_ed_scalar_mul_ltr_bin, p, k, out, n);
+    if (flags == ZC_SCALAR_MUL_BINARY_NAF) return scalar_mul_variant(ctx, zc::k_ed_scalar_mul_naf, p, k, out, n);
     return fail(ZC_ERR_BAD_ARG, "unknown scalar_mul flags");
 }
 // out[i] = sum_j k[i][j] * P[i][j]: one shared doubling chain per row (zc_curve.hip.h: lincomb_fast)
 int zc_ed_lincomb(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, size_t terms, uint64_t* out, size_t n)
 {
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    REQUIRE(points); REQUIRE(scalars); REQUIRE(out);
     if (terms < 1 || terms > ZC_LINCOMB_MAX_TERMS) return fail(ZC_ERR_BAD_ARG, "zc_ed_lincomb: terms must be 1..ZC_LINCOMB_MAX_TERMS");
     if (n >= ((size_t)1 << 31) / terms + (((size_t)1 << 31) % terms != 0)) return fail(ZC_ERR_BAD_ARG, "zc_ed_lincomb: n * terms must stay below 2^31");
-    Arg args[3] = {in_arg(points, 160 * terms), in_arg(scalars, 40 * terms), out_arg(out, 160)};
-    int inner = ZC_OK;
-    int rc = run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, const u64* dk, u64* dout) -> int {
         // five and more terms: 128-lane workgroups keep a workgroup's LDS (36 bytes per lane and term) below 37 KB
         const unsigned block = terms > 4 ? 128u : (unsigned)zc::ZC_BLOCK;
         const zc::u32 units = (zc::u32)ring_units_per_xcd(terms);
-        inner = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
-            hipLaunchKernelGGL(zc::k_ed_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * terms * block, D.s(),
-                               (const u64*)d[0] + 20 * terms * off, (const u64*)d[1] + 5 * terms * off, (zc::u32)terms, (u64*)d[2] + 20 * off,
-                               table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
-        }, terms);
-        if (inner == ZC_OK)
-            hipLaunchKernelGGL(zc::k_ed_lincomb_off_curve_rows, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1],
-                               (zc::u32)terms, (u64*)d[2], (zc::u32)cnt);
-    }, true);
-    return rc ? rc : inner;
+        if (int rc = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+                hipLaunchKernelGGL(zc::k_ed_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * terms * block, D.s(),
+                                   dp + 20 * terms * off, dk + 5 * terms * off, (zc::u32)terms, dout + 20 * off, table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
+            }, terms))
+            return rc;
+        hipLaunchKernelGGL(zc::k_ed_lincomb_off_curve_rows, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dp, dk, (zc::u32)terms, dout, (zc::u32)cnt);
+        return ZC_OK;
+    }, ROWS(points, 20 * terms), ROWS(scalars, 5 * terms), ROWS(out, 20));
 }
 int zc_ed_mul_by_pow_2(zc_ctx* ctx, const uint64_t* p, uint64_t kexp, uint64_t* out, size_t n)
 {
@@ -1526,165 +1534,61 @@ int zc_ed_mul_by_cofactor(zc_ctx* ctx, const uint64_t* p, uint64_t* out, size_t 
 }
 int zc_ed_to_affine(zc_ctx* ctx, const uint64_t* p, uint64_t* xy, uint8_t* ok, size_t n)
 {
-    REQUIRE(p); REQUIRE(xy);
-    Arg args[3] = {in_arg(p, 160), out_arg(xy, 80), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        const size_t c = inv_chunk(cnt, D.tune);
-        if (c < 2) {
-            hipLaunchKernelGGL(zc::k_ed_to_affine, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt);
-        } else {
-            const size_t lanes = (cnt + c - 1) / c;
-            hipLaunchKernelGGL(zc::k_ed_to_affine_chunked, dim3(grid_for(lanes)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt, (int)c);
-        }
-    });
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* dp, u64* dxy, uint8_t* dok) {
+        // (one chunked kernel at every size, and a 160-byte row cannot be normalised in place)
+        return launch_shared_inversions(D, cnt, false, zc::k_ed_to_affine, zc::k_ed_to_affine_chunked, zc::k_ed_to_affine_chunked, dp, dxy, dok);
+    }, ROWS(p, 20), ROWS(xy, 10), OPT_ROWS(ok, 1));
 }
-int zc_ed_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n)
-{
-    REQUIRE(p); REQUIRE(q); REQUIRE(eq);
-    Arg args[3] = {in_arg(p, 160), in_arg(q, 160), out_arg(eq, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ed_eq, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (uint8_t*)d[2], cnt);
-    });
-}
+int zc_ed_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n) { return batched(ctx, n, false, plain(zc::k_ed_eq), ROWS(p, 20), ROWS(q, 20), ROWS(eq, 1)); }
 int zc_ed_compress(zc_ctx* ctx, const uint64_t* p, uint8_t* out32, uint8_t* ok, size_t n)
 {
-    REQUIRE(p); REQUIRE(out32);
-    Arg args[3] = {in_arg(p, 160), out_arg(out32, 32), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ed_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_ed_compress), ROWS(p, 20), ROWS(out32, 32), OPT_ROWS(ok, 1));
 }
 int zc_ed_decompress(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* ok, size_t n)
 {
-    REQUIRE(in32); REQUIRE(out);
-    Arg args[3] = {in_arg(in32, 32), out_arg(out, 160), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ed_decompress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_ed_decompress), ROWS(in32, 32), ROWS(out, 20), OPT_ROWS(ok, 1));
 }
 
 // ---- Ristretto
-int zc_ris_compress(zc_ctx* ctx, const uint64_t* p, uint8_t* out32, size_t n)
-{
-    REQUIRE(p); REQUIRE(out32);
-    Arg args[2] = {in_arg(p, 160), out_arg(out32, 32)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ris_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
+int zc_ris_compress(zc_ctx* ctx, const uint64_t* p, uint8_t* out32, size_t n) { return batched(ctx, n, false, plain(zc::k_ris_compress), ROWS(p, 20), ROWS(out32, 32)); }
 int zc_ris_decompress(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* ok, size_t n)
 {
-    REQUIRE(in32); REQUIRE(out);
-    Arg args[3] = {in_arg(in32, 32), out_arg(out, 160), out_arg(ok, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ris_decompress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0], (u64*)d[1], (uint8_t*)d[2], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_ris_decompress), ROWS(in32, 32), ROWS(out, 20), OPT_ROWS(ok, 1));
 }
-int zc_ris_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n)
-{
-    REQUIRE(p); REQUIRE(q); REQUIRE(eq);
-    Arg args[3] = {in_arg(p, 160), in_arg(q, 160), out_arg(eq, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ris_eq, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (uint8_t*)d[2], cnt);
-    });
-}
+int zc_ris_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n) { return batched(ctx, n, false, plain(zc::k_ris_eq), ROWS(p, 20), ROWS(q, 20), ROWS(eq, 1)); }
 int zc_ris_roundtrip_mul(zc_ctx* ctx, const uint8_t* in32, const uint64_t* k, uint8_t* out32, uint8_t* ok, size_t n)
 {
-    REQUIRE(in32); REQUIRE(k); REQUIRE(out32);
-    Arg args[4] = {in_arg(in32, 32), in_arg(k, 40), out_arg(out32, 32), out_arg(ok, 1)};
     // The boundary is encodings in / encodings out, which depend only on the group element, so
     // the fast scalar-mul core is used (ZC_RISTRETTO_STRICT=1 runs the reference formula sequence).
-    int inner = ZC_OK;
-    int rc = run_batched(ctx, args, 4, n, [&](void** d, size_t cnt, DevState& D) {
-        if (D.tune.ristretto_strict) {
-            hipLaunchKernelGGL(zc::k_ris_roundtrip_mul, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0], (const u64*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], cnt);
-            return;
-        }
-        inner = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
-            hipLaunchKernelGGL(zc::k_ris_roundtrip_mul_fast, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0] + 32 * off,
-                               (const u64*)d[1] + 5 * off, (uint8_t*)d[2] + 32 * off, d[3] ? (uint8_t*)d[3] + off : (uint8_t*)nullptr, table, ring, slots, (zc::u32)c);
+    return batched(ctx, n, true, [](DevState& D, size_t cnt, const uint8_t* din, const u64* dk, uint8_t* dout, uint8_t* dok) {
+        if (D.tune.ristretto_strict) return plain(zc::k_ris_roundtrip_mul)(D, cnt, din, dk, dout, dok);
+        return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ris_roundtrip_mul_fast, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), din + 32 * off, dk + 5 * off, dout + 32 * off,
+                               dok ? dok + off : nullptr, table, ring, slots, (zc::u32)c);
         });
-    }, true);
-    return rc ? rc : inner;
+    }, ROWS(in32, 32), ROWS(k, 5), ROWS(out32, 32), OPT_ROWS(ok, 1));
 }
 
 // ---- "next" rows (N3, N4)
-int zc_ed_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n)
-{
-    REQUIRE(p); REQUIRE(valid);
-    Arg args[2] = {in_arg(p, 160), out_arg(valid, 1)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ed_is_valid, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
-int zc_ris_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n)
-{
-    REQUIRE(p); REQUIRE(valid);
-    Arg args[2] = {in_arg(p, 160), out_arg(valid, 1)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ris_is_valid, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
-int zc_ris_elligator(zc_ctx* ctx, const uint64_t* r0, uint64_t* out, size_t n)
-{
-    REQUIRE(r0); REQUIRE(out);
-    Arg args[2] = {in_arg(r0, 40), out_arg(out, 160)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ris_elligator, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], cnt);
-    });
-}
+int zc_ed_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n) { return batched(ctx, n, false, plain(zc::k_ed_is_valid), ROWS(p, 20), ROWS(valid, 1)); }
+int zc_ris_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n) { return batched(ctx, n, false, plain(zc::k_ris_is_valid), ROWS(p, 20), ROWS(valid, 1)); }
+int zc_ris_elligator(zc_ctx* ctx, const uint64_t* r0, uint64_t* out, size_t n) { return batched(ctx, n, false, plain(zc::k_ris_elligator), ROWS(r0, 5), ROWS(out, 20)); }
 int zc_ris_from_uniform_bytes(zc_ctx* ctx, const uint8_t* in64, uint64_t* out, size_t n)
 {
-    REQUIRE(in64); REQUIRE(out);
-    Arg args[2] = {in_arg(in64, 64), out_arg(out, 160)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ris_from_uniform_bytes, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)d[0], (u64*)d[1], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_ris_from_uniform_bytes), ROWS(in64, 64), ROWS(out, 20));
 }
-int zc_proj_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_proj_add, nullptr, p, q, o, n, 120); }
-int zc_proj_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_proj_double, p, o, n, 120); }
-int zc_proj_to_extended(zc_ctx* ctx, const uint64_t* p, uint64_t* out, size_t n)
-{
-    REQUIRE(p); REQUIRE(out);
-    Arg args[2] = {in_arg(p, 120), out_arg(out, 160)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_proj_to_extended, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], cnt);
-    });
-}
+int zc_proj_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_proj_add, p, q, o, n, 15); }
+int zc_proj_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_proj_double, p, o, n, 15); }
+int zc_proj_to_extended(zc_ctx* ctx, const uint64_t* p, uint64_t* out, size_t n) { return batched(ctx, n, false, plain(zc::k_proj_to_extended), ROWS(p, 15), ROWS(out, 20)); }
 // E-x rows: coset4 and the remaining ProjectivePoint operations
-int zc_ed_coset4(zc_ctx* ctx, const uint64_t* p, uint64_t* out4, size_t n)
-{
-    REQUIRE(p); REQUIRE(out4);
-    Arg args[2] = {in_arg(p, 160), out_arg(out4, 640)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_ed_coset4, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], cnt);
-    });
-}
-int zc_proj_neg(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_proj_neg, p, o, n, 120); }
-int zc_proj_sub(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_proj_sub, nullptr, p, q, o, n, 120); }
-int zc_proj_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n)
-{
-    REQUIRE(p); REQUIRE(q); REQUIRE(eq);
-    Arg args[3] = {in_arg(p, 120), in_arg(q, 120), out_arg(eq, 1)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_proj_eq, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (uint8_t*)d[2], cnt);
-    });
-}
-int zc_proj_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n)
-{
-    REQUIRE(p); REQUIRE(valid);
-    Arg args[2] = {in_arg(p, 120), out_arg(valid, 1)};
-    return run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_proj_is_valid, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], cnt);
-    });
-}
+int zc_ed_coset4(zc_ctx* ctx, const uint64_t* p, uint64_t* out4, size_t n) { return batched(ctx, n, false, plain(zc::k_ed_coset4), ROWS(p, 20), ROWS(out4, 80)); }
+int zc_proj_neg(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_proj_neg, p, o, n, 15); }
+int zc_proj_sub(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_proj_sub, p, q, o, n, 15); }
+int zc_proj_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n) { return batched(ctx, n, false, plain(zc::k_proj_eq), ROWS(p, 15), ROWS(q, 15), ROWS(eq, 1)); }
+int zc_proj_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n) { return batched(ctx, n, false, plain(zc::k_proj_is_valid), ROWS(p, 15), ROWS(valid, 1)); }
 int zc_proj_scalar_mul(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t* out, size_t n)
 {
-    REQUIRE(p); REQUIRE(k); REQUIRE(out);
-    Arg args[3] = {in_arg(p, 120), in_arg(k, 40), out_arg(out, 120)};
-    return run_batched(ctx, args, 3, n, [&](void** d, size_t cnt, DevState& D) {
-        hipLaunchKernelGGL(zc::k_proj_scalar_mul, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (const u64*)d[1], (u64*)d[2], cnt);
-    });
+    return batched(ctx, n, false, plain(zc::k_proj_scalar_mul), ROWS(p, 15), ROWS(k, 5), ROWS(out, 15));
 }
 
 // ---- fixed-base multiplication of the basepoint
@@ -1701,27 +1605,21 @@ static int base_table(DevState& D, const zc::u32** table)
 }
 int zc_ed_mul_base(zc_ctx* ctx, const uint64_t* k, uint64_t* out, size_t n)
 {
-    REQUIRE(k); REQUIRE(out);
-    Arg args[2] = {in_arg(k, 40), out_arg(out, 160)};
-    int inner = ZC_OK;
-    int rc = run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* dk, u64* dout) -> int {
         const zc::u32* t = nullptr;
-        if ((inner = base_table(D, &t)) != ZC_OK) return;
-        hipLaunchKernelGGL(zc::k_ed_mul_base, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (u64*)d[1], t, cnt);
-    });
-    return rc ? rc : inner;
+        if (int rc = base_table(D, &t)) return rc;
+        hipLaunchKernelGGL(zc::k_ed_mul_base, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, cnt);
+        return ZC_OK;
+    }, ROWS(k, 5), ROWS(out, 20));
 }
 int zc_ris_mul_base_compress(zc_ctx* ctx, const uint64_t* k, uint8_t* out32, size_t n)
 {
-    REQUIRE(k); REQUIRE(out32);
-    Arg args[2] = {in_arg(k, 40), out_arg(out32, 32)};
-    int inner = ZC_OK;
-    int rc = run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* dk, uint8_t* dout) -> int {
         const zc::u32* t = nullptr;
-        if ((inner = base_table(D, &t)) != ZC_OK) return;
-        hipLaunchKernelGGL(zc::k_ris_mul_base_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (uint8_t*)d[1], t, cnt);
-    });
-    return rc ? rc : inner;
+        if (int rc = base_table(D, &t)) return rc;
+        hipLaunchKernelGGL(zc::k_ris_mul_base_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, cnt);
+        return ZC_OK;
+    }, ROWS(k, 5), ROWS(out32, 32));
 }
 // out32[i] = compress(base_scalars[i] * B + sum_j scalars[i][j] * decompress(in32[i][j])): zc_ed_lincomb's windowed core between
 // the two codecs, the basepoint term from the comb table (zc_kernels.hip.h: k_ris_lincomb)
@@ -1729,45 +1627,37 @@ int zc_ris_lincomb(zc_ctx* ctx, const uint8_t* in32, const uint64_t* scalars, si
                    uint8_t* ok, size_t n)
 {
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    REQUIRE(in32); REQUIRE(scalars); REQUIRE(out32);
     const size_t slots_used = terms + (base_scalars ? 1 : 0);             // the base term takes one of the scalar slots
     if (terms < 1 || terms > ZC_LINCOMB_MAX_TERMS || slots_used > ZC_LINCOMB_MAX_TERMS)
         return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb: terms must be at least 1, terms + (base_scalars != NULL) at most ZC_LINCOMB_MAX_TERMS");
     if (n >= ((size_t)1 << 31) / terms + (((size_t)1 << 31) % terms != 0)) return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb: n * terms must stay below 2^31");
-    Arg args[5] = {in_arg(in32, 32 * terms), in_arg(scalars, 40 * terms), in_arg(base_scalars, 40), out_arg(out32, 32), out_arg(ok, 1)};
-    int inner = ZC_OK;
-    int rc = run_batched(ctx, args, 5, n, [&](void** d, size_t cnt, DevState& D) {
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const uint8_t* din, const u64* dk, const u64* dbase, uint8_t* dout, uint8_t* dok) -> int {
         const zc::u32* comb = nullptr;
-        if (d[2] && (inner = base_table(D, &comb)) != ZC_OK) return;
+        if (dbase)
+            if (int rc = base_table(D, &comb)) return rc;
         // as zc_ed_lincomb: 128-lane workgroups from five scalar slots on (36 bytes of LDS per lane and slot)
         const unsigned block = slots_used > 4 ? 128u : (unsigned)zc::ZC_BLOCK;
         const zc::u32 units = (zc::u32)ring_units_per_xcd(terms);
-        inner = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+        return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
             hipLaunchKernelGGL(zc::k_ris_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * slots_used * block, D.s(),
-                               (const uint8_t*)d[0] + 32 * terms * off, (const u64*)d[1] + 5 * terms * off, (zc::u32)terms,
-                               d[2] ? (const u64*)d[2] + 5 * off : (const u64*)nullptr, (uint8_t*)d[3] + 32 * off,
-                               d[4] ? (uint8_t*)d[4] + off : (uint8_t*)nullptr, comb, table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
+                               din + 32 * terms * off, dk + 5 * terms * off, (zc::u32)terms, dbase ? dbase + 5 * off : nullptr, dout + 32 * off,
+                               dok ? dok + off : nullptr, comb, table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
         }, terms);
-    }, true);
-    return rc ? rc : inner;
+    }, ROWS(in32, 32 * terms), ROWS(scalars, 5 * terms), OPT_ROWS(base_scalars, 5), ROWS(out32, 32), OPT_ROWS(ok, 1));
 }
 
 // window_naf_mul (src/edwards.rs:155-171) with its table indexed correctly: see k_ed_mul_base_wnaf
 int zc_ed_mul_base_wnaf(zc_ctx* ctx, const uint64_t* k, unsigned width, uint64_t* out, size_t n)
 {
-    REQUIRE(k); REQUIRE(out);
     if (width < 2 || width > 7) return fail(ZC_ERR_BAD_ARG, "zc_ed_mul_base_wnaf: window width 2..7 (compute_window_NAF's digits are i8)");
-    Arg args[2] = {in_arg(k, 40), out_arg(out, 160)};
-    int inner = ZC_OK;
-    int rc = run_batched(ctx, args, 2, n, [&](void** d, size_t cnt, DevState& D) {
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, u64* dout) -> int {
         if (!D.odd_table) {
-            if ((inner = ensure(&D.odd_table, &D.odd_bytes, (size_t)zc::ZC_ODD_ENTRIES * 128)) != ZC_OK) return;
+            if (int rc = ensure(&D.odd_table, &D.odd_bytes, (size_t)zc::ZC_ODD_ENTRIES * 128)) return rc;
             hipLaunchKernelGGL(zc::k_odd_table_build, dim3(1), dim3(128), 0, D.s(), (zc::u32*)D.odd_table);
         }
-        hipLaunchKernelGGL(zc::k_ed_mul_base_wnaf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)d[0], (zc::u32)width, (u64*)d[1],
-                           (const zc::u32*)D.odd_table, cnt);
-    });
-    return rc ? rc : inner;
+        hipLaunchKernelGGL(zc::k_ed_mul_base_wnaf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, (zc::u32)width, dout, (const zc::u32*)D.odd_table, cnt);
+        return ZC_OK;
+    }, ROWS(k, 5), ROWS(out, 20));
 }
 
 // ---- MSM: sum_i k_i * P_i (not in the reference; specified as the reference's own

@@ -20,6 +20,8 @@ LTR_BIN = 1         # ltr_bin_mul
 BINARY_NAF = 2      # binary_naf_mul
 FAST = 16           # same group element, not limb-exact (windowed, dedicated doubling)
 
+U64, U8 = np.dtype(np.uint64), np.dtype(np.uint8)
+
 
 def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "device")
@@ -100,44 +102,67 @@ class Engine:
         _lib.check(self.lib.zc_ctx_synchronize(self.ctx), "zc_ctx_synchronize", self.lib)
 
     # ------------------------------------------------------------------ helpers
-    def _prep(self, x, width, dtype):
+    def _prep(self, x, width, dtype, lead=1):
+        """Rows of shape (n, [t,] width) -- `lead` leading dimensions -- as the library reads them: a contiguous numpy array
+        of `dtype` (converted when it is not), or a contiguous torch tensor with elements of that size, used in place on
+        torch's current stream.  Returns (array, pointer, leading shape)."""
         if _is_torch(x):
-            assert x.is_contiguous() and x.shape[-1] == width, (x.shape, width)
-            assert x.element_size() == np.dtype(dtype).itemsize
+            shape = x.shape
+            assert x.is_contiguous() and len(shape) == lead + 1 and shape[-1] == width, (shape, lead, width)
+            assert x.element_size() == dtype.itemsize
             self._follow_torch_stream(x)
-            return x, x.data_ptr(), x.shape[0]
+            return x, x.data_ptr(), shape[:lead]
         a = np.ascontiguousarray(x, dtype=dtype)
-        assert a.ndim == 2 and a.shape[1] == width, (a.shape, width)
-        return a, a.ctypes.data, a.shape[0]
+        assert a.ndim == lead + 1 and a.shape[-1] == width, (a.shape, lead, width)
+        return a, a.ctypes.data, a.shape[:lead]
+
+    def _inputs(self, ins, lead=1):
+        """_prep for every (array, width, dtype) of `ins`, which must agree in their leading shape:
+        (arrays, pointers, that shape)."""
+        arrs, ptrs, shape = [], [], None
+        for x, w, dt in ins:
+            a, p, s = self._prep(x, w, dt, lead)
+            assert shape is None or s == shape, "row counts differ: %s, %s" % (shape, s)
+            shape = s
+            arrs.append(a)
+            ptrs.append(p)
+        return arrs, ptrs, shape
 
     @staticmethod
     def _alloc(like, n, width, dtype):
+        """An output of n rows (width 0: a flat array) of the kind of `like`.  Tensors: uint8 for bytes, else the input's own
+        8-byte dtype, or int64 when it has none."""
+        shape = (n, width) if width else (n,)
         if _is_torch(like):
             import torch
-            tdt = torch.uint8 if np.dtype(dtype) == np.uint8 else like.dtype if like.element_size() == 8 else torch.int64
-            shape = (n, width) if width else (n,)
+            tdt = torch.uint8 if dtype == U8 else like.dtype if like.element_size() == 8 else torch.int64
             t = torch.empty(shape, dtype=tdt, device=like.device)
             return t, t.data_ptr()
-        shape = (n, width) if width else (n,)
         a = np.empty(shape, dtype=dtype)
         return a, a.ctypes.data
 
     def _call(self, name, *args):
         _lib.check(getattr(self.lib, name)(self.ctx, *args), name, self.lib)
 
-    def _bin(self, name, a, b, w):
-        a, pa, n = self._prep(a, w, np.uint64)
-        b, pb, nb = self._prep(b, w, np.uint64)
-        assert n == nb
-        out, po = self._alloc(a, n, w, np.uint64)
-        self._call(name, pa, pb, po, n)
-        return out
+    def _rows(self, name, ins, outs, mid=(), tail=(), out=None):
+        """One batched entry point, name(ctx, inputs..., mid..., outputs..., n, tail...): `ins` = (array, width, dtype) per
+        input, `outs` = (width, dtype) per output, allocated like the first input -- except the first when the caller
+        brings it (`out`).  Returns the output, or the tuple of them."""
+        if out is not None:
+            ins = ins + [(out, outs[0][0], outs[0][1])]
+        arrs, ptrs, shape = self._inputs(ins)
+        n = shape[0]
+        res = [self._alloc(arrs[0], n, w, dt) for w, dt in outs]
+        if out is not None:
+            res[0] = (arrs.pop(), ptrs.pop())
+        self._call(name, *ptrs, *mid, *[p for _, p in res], n, *tail)
+        return res[0][0] if len(res) == 1 else tuple(a for a, _ in res)
 
-    def _un(self, name, a, w):
-        a, pa, n = self._prep(a, w, np.uint64)
-        out, po = self._alloc(a, n, w, np.uint64)
-        self._call(name, pa, po, n)
-        return out
+    def _bin(self, name, a, b, w): return self._rows(name, [(a, w, U64), (b, w, U64)], [(w, U64)])
+    def _un(self, name, a, w): return self._rows(name, [(a, w, U64)], [(w, U64)])
+    def _flag(self, name, a, w): return self._rows(name, [(a, w, U64)], [(0, U8)])
+    def _checked(self, name, a, w, wout, dt=U64): return self._rows(name, [(a, w, U64)], [(wout, dt), (0, U8)])
+    def _decode(self, name, b, wout): return self._rows(name, [(b, 32, U8)], [(wout, U64), (0, U8)])
 
     # ------------------------------------------------------------------ FieldElement (field.rs)
     def fe_add(self, a, b): return self._bin("zc_fe_add", a, b, 5)
@@ -145,76 +170,20 @@ class Engine:
     def fe_mul(self, a, b): return self._bin("zc_fe_mul", a, b, 5)
     def fe_neg(self, a): return self._un("zc_fe_neg", a, 5)
     def fe_square(self, a): return self._un("zc_fe_square", a, 5)
-
-    def fe_invert(self, a):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 5, np.uint64)
-        ok, pk = self._alloc(a, n, 0, np.uint8)
-        self._call("zc_fe_invert", pa, po, pk, n)
-        return out, ok
-
-    def fe_div(self, a, b):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        b, pb, _ = self._prep(b, 5, np.uint64)
-        out, po = self._alloc(a, n, 5, np.uint64)
-        ok, pk = self._alloc(a, n, 0, np.uint8)
-        self._call("zc_fe_div", pa, pb, po, pk, n)
-        return out, ok
-
+    def fe_invert(self, a): return self._checked("zc_fe_invert", a, 5, 5)
+    def fe_div(self, a, b): return self._rows("zc_fe_div", [(a, 5, U64), (b, 5, U64)], [(5, U64), (0, U8)])
     def fe_half(self, a): return self._un("zc_fe_half", a, 5)
     def fe_pow(self, a, e): return self._bin("zc_fe_pow", a, e, 5)
-
-    def _fe_flag(self, name, a):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 0, np.uint8)
-        self._call(name, pa, po, n)
-        return out
-
-    def fe_legendre_symbol(self, a): return self._fe_flag("zc_fe_legendre_symbol", a)
-    def fe_is_positive(self, a): return self._fe_flag("zc_fe_is_positive", a)
-
-    def fe_mod_sqrt(self, a, sign):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 5, np.uint64)
-        ok, pk = self._alloc(a, n, 0, np.uint8)
-        self._call("zc_fe_mod_sqrt", pa, C.c_int(int(sign)), po, pk, n)
-        return out, ok
-
-    def fe_from_bytes(self, b):
-        b, pb, n = self._prep(b, 32, np.uint8)
-        out, po = self._alloc_u64(b, n, 5)
-        self._call("zc_fe_from_bytes", pb, po, n)
-        return out
-
-    def fe_to_bytes(self, a):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 32, np.uint8)
-        self._call("zc_fe_to_bytes", pa, po, n)
-        return out
-
-    def fe_sqrt_ratio_i(self, u, v):
-        u, pu, n = self._prep(u, 5, np.uint64)
-        v, pv, _ = self._prep(v, 5, np.uint64)
-        out, po = self._alloc(u, n, 5, np.uint64)
-        sq, ps = self._alloc(u, n, 0, np.uint8)
-        self._call("zc_fe_sqrt_ratio_i", pu, pv, po, ps, n)
-        return out, sq
+    def fe_legendre_symbol(self, a): return self._flag("zc_fe_legendre_symbol", a, 5)
+    def fe_is_positive(self, a): return self._flag("zc_fe_is_positive", a, 5)
+    def fe_mod_sqrt(self, a, sign): return self._rows("zc_fe_mod_sqrt", [(a, 5, U64)], [(5, U64), (0, U8)], mid=(C.c_int(int(sign)),))
+    def fe_from_bytes(self, b): return self._rows("zc_fe_from_bytes", [(b, 32, U8)], [(5, U64)])
+    def fe_to_bytes(self, a): return self._rows("zc_fe_to_bytes", [(a, 5, U64)], [(32, U8)])
+    def fe_sqrt_ratio_i(self, u, v): return self._rows("zc_fe_sqrt_ratio_i", [(u, 5, U64), (v, 5, U64)], [(5, U64), (0, U8)])
 
     def fe_inv_sqrt(self, a):
         """InvSqrt (field.rs:443-460): (1/sqrt(a) or sqrt(i/a), was_square)."""
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 5, np.uint64)
-        sq, ps = self._alloc(a, n, 0, np.uint8)
-        self._call("zc_fe_inv_sqrt", pa, po, ps, n)
-        return out, sq
-
-    def _alloc_u64(self, like, n, width):
-        if _is_torch(like):
-            import torch
-            t = torch.empty((n, width), dtype=torch.int64, device=like.device)
-            return t, t.data_ptr()
-        a = np.empty((n, width), dtype=np.uint64)
-        return a, a.ctypes.data
+        return self._checked("zc_fe_inv_sqrt", a, 5, 5)
 
     # ------------------------------------------------------------------ Scalar (scalar.rs)
     def sc_add(self, a, b): return self._bin("zc_sc_add", a, b, 5)
@@ -226,42 +195,22 @@ class Engine:
     # the Scalar operations beside the default scalar-mul path (scalar.rs:165-182, 285-322, 352-415)
     def sc_half(self, a): return self._un("zc_sc_half", a, 5)
     def sc_pow(self, a, e): return self._bin("zc_sc_pow", a, e, 5)
-
-    def sc_shr(self, a, shift):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 5, np.uint64)
-        self._call("zc_sc_shr", pa, C.c_uint(int(shift)), po, n)
-        return out
+    def sc_shr(self, a, shift): return self._rows("zc_sc_shr", [(a, 5, U64)], [(5, U64)], mid=(C.c_uint(int(shift)),))
 
     def sc_into_bits(self, a):
         """into_bits: (n, 256) uint8, the bits of to_bytes(), least significant first."""
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 256, np.uint8)
-        self._call("zc_sc_into_bits", pa, po, n)
-        return out
+        return self._rows("zc_sc_into_bits", [(a, 5, U64)], [(256, U8)])
 
     def sc_compute_naf(self, a, width=0):
         """compute_NAF (width 0) / compute_window_NAF(width 2..7): (n, 256) int8 digits."""
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 256, np.uint8)
-        self._call("zc_sc_compute_naf", pa, C.c_uint(int(width)), po, n)
+        out = self._rows("zc_sc_compute_naf", [(a, 5, U64)], [(256, U8)], mid=(C.c_uint(int(width)),))
         if _is_torch(out):
             import torch
             return out.view(torch.int8)
         return out.view(np.int8)
 
-    def sc_from_bytes(self, b):
-        b, pb, n = self._prep(b, 32, np.uint8)
-        out, po = self._alloc_u64(b, n, 5)
-        ok, pk = self._alloc(b, n, 0, np.uint8)
-        self._call("zc_sc_from_bytes", pb, po, pk, n)
-        return out, ok
-
-    def sc_to_bytes(self, a):
-        a, pa, n = self._prep(a, 5, np.uint64)
-        out, po = self._alloc(a, n, 32, np.uint8)
-        self._call("zc_sc_to_bytes", pa, po, n)
-        return out
+    def sc_from_bytes(self, b): return self._decode("zc_sc_from_bytes", b, 5)
+    def sc_to_bytes(self, a): return self._rows("zc_sc_to_bytes", [(a, 5, U64)], [(32, U8)])
 
     # ------------------------------------------------------------------ EdwardsPoint (edwards.rs)
     def ed_add(self, p, q): return self._bin("zc_ed_add", p, q, 20)
@@ -270,109 +219,36 @@ class Engine:
     def ed_neg(self, p): return self._un("zc_ed_neg", p, 20)
 
     def ed_scalar_mul(self, p, k, out=None, flags=STRICT):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        k, pk, nk = self._prep(k, 5, np.uint64)
-        assert n == nk
-        if out is None:
-            out, po = self._alloc(p, n, 20, np.uint64)
-        else:
-            out, po, _ = self._prep(out, 20, np.uint64)
-        self._call("zc_ed_scalar_mul", pp, pk, po, n, flags)
-        return out
+        return self._rows("zc_ed_scalar_mul", [(p, 20, U64), (k, 5, U64)], [(20, U64)], tail=(flags,), out=out)
+
+    def _same_kind(self, who, *arrays):
+        assert all(_is_torch(x) == _is_torch(arrays[0]) for x in arrays), who + ": the arrays must all be numpy arrays or all torch tensors"
 
     def ed_lincomb(self, points, scalars):
         """out[i] = sum_j scalars[i, j] * points[i, j] (zc_ed_lincomb): (n, t, 20) points and (n, t, 5) scalars, t = 1..8 --
         numpy arrays, or contiguous torch tensors on one device (the call then runs on torch's current stream and the result
         stays on the device) -> (n, 20) of the same kind.  One doubling chain per row is shared by its terms; the result is
         the same group element as the composition of ed_scalar_mul and ed_add (ed_eq / encodings), not the same limbs."""
-        tensors = _is_torch(points)
-        assert tensors == _is_torch(scalars), "ed_lincomb: points and scalars must both be numpy arrays or both torch tensors"
-        if not tensors:
-            points, scalars = np.ascontiguousarray(points, dtype=np.uint64), np.ascontiguousarray(scalars, dtype=np.uint64)
-        assert points.ndim == 3 and scalars.ndim == 3 and points.shape[2] == 20 and scalars.shape[2] == 5, (points.shape, scalars.shape)
-        assert tuple(points.shape[:2]) == tuple(scalars.shape[:2]), (points.shape, scalars.shape)
-        n, t = int(points.shape[0]), int(points.shape[1])
-        if tensors:
-            assert points.is_contiguous() and scalars.is_contiguous() and points.element_size() == 8 and scalars.element_size() == 8
-            self._follow_torch_stream(points)
-            pp, pk = points.data_ptr(), scalars.data_ptr()
-        else:
-            pp, pk = points.ctypes.data, scalars.ctypes.data
-        out, po = self._alloc(points, n, 20, np.uint64)
+        self._same_kind("ed_lincomb", points, scalars)
+        (points, _), (pp, pk), (n, t) = self._inputs([(points, 20, U64), (scalars, 5, U64)], lead=2)
+        out, po = self._alloc(points, n, 20, U64)
         self._call("zc_ed_lincomb", pp, pk, t, po, n)
         return out
 
-    def ed_mul_by_pow_2(self, p, kexp):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        out, po = self._alloc(p, n, 20, np.uint64)
-        self._call("zc_ed_mul_by_pow_2", pp, C.c_uint64(kexp), po, n)
-        return out
-
-    def ed_mul_by_cofactor(self, p):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        out, po = self._alloc(p, n, 20, np.uint64)
-        self._call("zc_ed_mul_by_cofactor", pp, po, n)
-        return out
-
-    def ed_to_affine(self, p):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        xy, px = self._alloc(p, n, 10, np.uint64)
-        ok, pk = self._alloc(p, n, 0, np.uint8)
-        self._call("zc_ed_to_affine", pp, px, pk, n)
-        return xy, ok
-
-    def ed_eq(self, p, q):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        q, pq, _ = self._prep(q, 20, np.uint64)
-        eq, pe = self._alloc(p, n, 0, np.uint8)
-        self._call("zc_ed_eq", pp, pq, pe, n)
-        return eq
-
-    def ed_compress(self, p):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        out, po = self._alloc(p, n, 32, np.uint8)
-        ok, pk = self._alloc(p, n, 0, np.uint8)
-        self._call("zc_ed_compress", pp, po, pk, n)
-        return out, ok
-
-    def ed_decompress(self, b):
-        b, pb, n = self._prep(b, 32, np.uint8)
-        out, po = self._alloc_u64(b, n, 20)
-        ok, pk = self._alloc(b, n, 0, np.uint8)
-        self._call("zc_ed_decompress", pb, po, pk, n)
-        return out, ok
+    def ed_mul_by_pow_2(self, p, kexp): return self._rows("zc_ed_mul_by_pow_2", [(p, 20, U64)], [(20, U64)], mid=(C.c_uint64(kexp),))
+    def ed_mul_by_cofactor(self, p): return self._un("zc_ed_mul_by_cofactor", p, 20)
+    def ed_to_affine(self, p): return self._checked("zc_ed_to_affine", p, 20, 10)
+    def ed_eq(self, p, q): return self._rows("zc_ed_eq", [(p, 20, U64), (q, 20, U64)], [(0, U8)])
+    def ed_compress(self, p): return self._checked("zc_ed_compress", p, 20, 32, U8)
+    def ed_decompress(self, b): return self._decode("zc_ed_decompress", b, 20)
 
     # ------------------------------------------------------------------ Ristretto (ristretto.rs)
-    def ris_compress(self, p):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        out, po = self._alloc(p, n, 32, np.uint8)
-        self._call("zc_ris_compress", pp, po, n)
-        return out
-
-    def ris_decompress(self, b):
-        b, pb, n = self._prep(b, 32, np.uint8)
-        out, po = self._alloc_u64(b, n, 20)
-        ok, pk = self._alloc(b, n, 0, np.uint8)
-        self._call("zc_ris_decompress", pb, po, pk, n)
-        return out, ok
-
-    def ris_eq(self, p, q):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        q, pq, _ = self._prep(q, 20, np.uint64)
-        eq, pe = self._alloc(p, n, 0, np.uint8)
-        self._call("zc_ris_eq", pp, pq, pe, n)
-        return eq
+    def ris_compress(self, p): return self._rows("zc_ris_compress", [(p, 20, U64)], [(32, U8)])
+    def ris_decompress(self, b): return self._decode("zc_ris_decompress", b, 20)
+    def ris_eq(self, p, q): return self._rows("zc_ris_eq", [(p, 20, U64), (q, 20, U64)], [(0, U8)])
 
     def ris_roundtrip_mul(self, b, k, out=None):
-        b, pb, n = self._prep(b, 32, np.uint8)
-        k, pk, _ = self._prep(k, 5, np.uint64)
-        if out is None:
-            out, po = self._alloc(b, n, 32, np.uint8)
-        else:
-            out, po, _ = self._prep(out, 32, np.uint8)
-        ok, pko = self._alloc(b, n, 0, np.uint8)
-        self._call("zc_ris_roundtrip_mul", pb, pk, po, pko, n)
-        return out, ok
+        return self._rows("zc_ris_roundtrip_mul", [(b, 32, U8), (k, 5, U64)], [(32, U8), (0, U8)], out=out)
 
     def ris_lincomb(self, enc, scalars, base_scalars=None):
         """out32[i] = compress(base_scalars[i] * B + sum_j scalars[i, j] * decompress(enc[i, j])) (zc_ris_lincomb): (n, t, 32)
@@ -380,105 +256,43 @@ class Engine:
         arrays, or contiguous torch tensors on one device (the call then runs on torch's current stream and the results stay
         on the device) -> ((n, 32) uint8, (n,) uint8 accept mask) of the same kind.  The bytes are those of the reference's
         decompress / Mul<Scalar> / + / compress; a row with an undecodable term is 32 zero bytes with ok = 0."""
-        given = [enc, scalars] + ([] if base_scalars is None else [base_scalars])
-        tensors = _is_torch(enc)
-        assert all(_is_torch(x) == tensors for x in given), "ris_lincomb: the arrays must all be numpy arrays or all torch tensors"
-        if not tensors:
-            enc, scalars = np.ascontiguousarray(enc, dtype=np.uint8), np.ascontiguousarray(scalars, dtype=np.uint64)
-            if base_scalars is not None:
-                base_scalars = np.ascontiguousarray(base_scalars, dtype=np.uint64)
-        assert enc.ndim == 3 and scalars.ndim == 3 and enc.shape[2] == 32 and scalars.shape[2] == 5, (enc.shape, scalars.shape)
-        assert tuple(enc.shape[:2]) == tuple(scalars.shape[:2]), (enc.shape, scalars.shape)
-        n, t = int(enc.shape[0]), int(enc.shape[1])
-        assert base_scalars is None or tuple(base_scalars.shape) == (n, 5), base_scalars.shape
-        if tensors:
-            assert enc.is_contiguous() and enc.element_size() == 1 and scalars.is_contiguous() and scalars.element_size() == 8
-            assert base_scalars is None or (base_scalars.is_contiguous() and base_scalars.element_size() == 8)
-            self._follow_torch_stream(enc)
-            pe, pk, pb = enc.data_ptr(), scalars.data_ptr(), None if base_scalars is None else base_scalars.data_ptr()
-        else:
-            pe, pk, pb = enc.ctypes.data, scalars.ctypes.data, None if base_scalars is None else base_scalars.ctypes.data
-        out, po = self._alloc(enc, n, 32, np.uint8)
-        ok, pko = self._alloc(enc, n, 0, np.uint8)
+        self._same_kind("ris_lincomb", enc, scalars, *([] if base_scalars is None else [base_scalars]))
+        (enc, _), (pe, pk), (n, t) = self._inputs([(enc, 32, U8), (scalars, 5, U64)], lead=2)
+        pb = None
+        if base_scalars is not None:
+            _, pb, nb = self._prep(base_scalars, 5, U64)
+            assert nb == (n,), "row counts differ: %s" % ((n, nb),)
+        out, po = self._alloc(enc, n, 32, U8)
+        ok, pko = self._alloc(enc, n, 0, U8)
         self._call("zc_ris_lincomb", pe, pk, t, pb, po, pko, n)
         return out, ok
 
     # ------------------------------------------------------------------ next rows (N3, N4)
-    def _flag(self, name, p):
-        p, pp, n = self._prep(p, 20, np.uint64)
-        v, pv = self._alloc(p, n, 0, np.uint8)
-        self._call(name, pp, pv, n)
-        return v
-
-    def ed_is_valid(self, p): return self._flag("zc_ed_is_valid", p)
-    def ris_is_valid(self, p): return self._flag("zc_ris_is_valid", p)
-
-    def ris_elligator(self, r0):
-        r0, pr, n = self._prep(r0, 5, np.uint64)
-        out, po = self._alloc(r0, n, 20, np.uint64)
-        self._call("zc_ris_elligator", pr, po, n)
-        return out
-
-    def ris_from_uniform_bytes(self, b):
-        b, pb, n = self._prep(b, 64, np.uint8)
-        out, po = self._alloc_u64(b, n, 20)
-        self._call("zc_ris_from_uniform_bytes", pb, po, n)
-        return out
-
+    def ed_is_valid(self, p): return self._flag("zc_ed_is_valid", p, 20)
+    def ris_is_valid(self, p): return self._flag("zc_ris_is_valid", p, 20)
+    def ris_elligator(self, r0): return self._rows("zc_ris_elligator", [(r0, 5, U64)], [(20, U64)])
+    def ris_from_uniform_bytes(self, b): return self._rows("zc_ris_from_uniform_bytes", [(b, 64, U8)], [(20, U64)])
     def proj_add(self, p, q): return self._bin("zc_proj_add", p, q, 15)
     def proj_double(self, p): return self._un("zc_proj_double", p, 15)
-
-    def proj_to_extended(self, p):
-        p, pp, n = self._prep(p, 15, np.uint64)
-        out, po = self._alloc(p, n, 20, np.uint64)
-        self._call("zc_proj_to_extended", pp, po, n)
-        return out
+    def proj_to_extended(self, p): return self._rows("zc_proj_to_extended", [(p, 15, U64)], [(20, U64)])
 
     # ProjectivePoint beside add / double (edwards.rs:701-748, 787-912) and EdwardsPoint::coset4 (:603-610)
     def proj_neg(self, p): return self._un("zc_proj_neg", p, 15)
     def proj_sub(self, p, q): return self._bin("zc_proj_sub", p, q, 15)
-
-    def proj_eq(self, p, q):
-        p, pp, n = self._prep(p, 15, np.uint64)
-        q, pq, _ = self._prep(q, 15, np.uint64)
-        eq, pe = self._alloc(p, n, 0, np.uint8)
-        self._call("zc_proj_eq", pp, pq, pe, n)
-        return eq
-
-    def proj_is_valid(self, p):
-        p, pp, n = self._prep(p, 15, np.uint64)
-        v, pv = self._alloc(p, n, 0, np.uint8)
-        self._call("zc_proj_is_valid", pp, pv, n)
-        return v
-
-    def proj_scalar_mul(self, p, k):
-        p, pp, n = self._prep(p, 15, np.uint64)
-        k, pk, nk = self._prep(k, 5, np.uint64)
-        assert n == nk
-        out, po = self._alloc(p, n, 15, np.uint64)
-        self._call("zc_proj_scalar_mul", pp, pk, po, n)
-        return out
+    def proj_eq(self, p, q): return self._rows("zc_proj_eq", [(p, 15, U64), (q, 15, U64)], [(0, U8)])
+    def proj_is_valid(self, p): return self._flag("zc_proj_is_valid", p, 15)
+    def proj_scalar_mul(self, p, k): return self._rows("zc_proj_scalar_mul", [(p, 15, U64), (k, 5, U64)], [(15, U64)])
 
     def ed_coset4(self, p):
         """coset4: (n, 80) uint64 = four points per input point."""
-        p, pp, n = self._prep(p, 20, np.uint64)
-        out, po = self._alloc(p, n, 80, np.uint64)
-        self._call("zc_ed_coset4", pp, po, n)
-        return out
+        return self._rows("zc_ed_coset4", [(p, 20, U64)], [(80, U64)])
 
     # ------------------------------------------------------------------ fixed-base (key generation)
-    def ed_mul_base(self, k):
-        k, pk, n = self._prep(k, 5, np.uint64)
-        out, po = self._alloc(k, n, 20, np.uint64)
-        self._call("zc_ed_mul_base", pk, po, n)
-        return out
+    def ed_mul_base(self, k): return self._rows("zc_ed_mul_base", [(k, 5, U64)], [(20, U64)])
 
     def ed_mul_base_wnaf(self, k, width):
         """window_naf_mul (edwards.rs:155-171) with the table indexed correctly, one launch; width 2..7."""
-        k, pk, n = self._prep(k, 5, np.uint64)
-        out, po = self._alloc(k, n, 20, np.uint64)
-        self._call("zc_ed_mul_base_wnaf", pk, int(width), po, n)
-        return out
+        return self._rows("zc_ed_mul_base_wnaf", [(k, 5, U64)], [(20, U64)], mid=(int(width),))
 
     def msm_plan(self, n, points_aligned16=True):
         """What the bucket method would do for a shard of n pairs on this context (a query, no device work)."""
@@ -489,18 +303,16 @@ class Engine:
                 "segment_buckets": v[5], "sort_passes": v[6], "window_groups": g,
                 "group_windows": [v[9 + i] for i in range(g)], "group_runs": [v[13 + i] for i in range(g)]}
 
-    def ris_mul_base_compress(self, k):
-        k, pk, n = self._prep(k, 5, np.uint64)
-        out, po = self._alloc(k, n, 32, np.uint8)
-        self._call("zc_ris_mul_base_compress", pk, po, n)
-        return out
+    def ris_mul_base_compress(self, k): return self._rows("zc_ris_mul_base_compress", [(k, 5, U64)], [(32, U8)])
 
     # ------------------------------------------------------------------ MSM (not in the reference)
+    def _msm(self, name, points, scalars, out_ptr):
+        _, (pp, pk), (n,) = self._inputs([(points, 20, U64), (scalars, 5, U64)])
+        self._call(name, pp, pk, n, out_ptr)
+
     def msm(self, points, scalars):
-        points, pp, n = self._prep(points, 20, np.uint64)
-        scalars, pk, _ = self._prep(scalars, 5, np.uint64)
         out = np.empty((1, 20), dtype=np.uint64)
-        self._call("zc_msm", pp, pk, n, out.ctypes.data)
+        self._msm("zc_msm", points, scalars, out.ctypes.data)
         return out
 
     def msm_bases(self, points, window_bits=0):
@@ -518,20 +330,9 @@ class Engine:
     def msm_batch(self, points, scalars):
         """`batch` independent MSMs (zc_msm_batch): (batch, n, 20) points and (batch, n, 5) scalars -- numpy, or torch tensors
         on one device of this context -- give a (batch, 20) numpy array, row b = sum_i scalars[b, i] * points[b, i]."""
-        ps, ks = tuple(points.shape), tuple(scalars.shape)
-        assert len(ps) == 3 and ps[2] == 20 and ks == ps[:2] + (5,), (ps, ks)
-        batch, n = ps[0], ps[1]
-        ptrs = []
-        for a in (points, scalars):
-            if _is_torch(a):
-                assert a.is_contiguous() and a.element_size() == 8
-                self._follow_torch_stream(a)
-                ptrs.append((a, a.data_ptr()))
-            else:
-                a = np.ascontiguousarray(a, dtype=np.uint64)
-                ptrs.append((a, a.ctypes.data))
+        _, (pp, pk), (batch, n) = self._inputs([(points, 20, U64), (scalars, 5, U64)], lead=2)
         out = np.empty((batch, 20), dtype=np.uint64)
-        self._call("zc_msm_batch", ptrs[0][1], ptrs[1][1], n, batch, out.ctypes.data)
+        self._call("zc_msm_batch", pp, pk, n, batch, out.ctypes.data)
         return out
 
     def msm_batch_plan(self, n, batch, points_aligned16=True):
@@ -545,19 +346,17 @@ class Engine:
     def msm_partial(self, points, scalars, out=None):
         """This device's sum left in device memory: a (1, 20) int64 torch CUDA tensor (asynchronous)."""
         import torch
-        points, pp, n = self._prep(points, 20, np.uint64)
-        scalars, pk, _ = self._prep(scalars, 5, np.uint64)
         if out is None:
             dev = points.device if _is_torch(points) else torch.device("cuda", torch.cuda.current_device())
             out = torch.empty((1, 20), dtype=torch.int64, device=dev)
             self._follow_torch_stream(out)
-        self._call("zc_msm_partial", pp, pk, n, out.data_ptr())
+        self._msm("zc_msm_partial", points, scalars, out.data_ptr())
         return out
 
     def ed_fold_ordered(self, parts):
         """((p_0 + p_1) + p_2) + ... in index order, one kernel launch; (count, 20) -> (1, 20)."""
-        parts, pp, n = self._prep(parts, 20, np.uint64)
-        out, po = self._alloc(parts, 1, 20, np.uint64)
+        parts, pp, (n,) = self._prep(parts, 20, U64)
+        out, po = self._alloc(parts, 1, 20, U64)
         self._call("zc_ed_fold_ordered", pp, n, po)
         return out
 
@@ -585,10 +384,8 @@ class Engine:
         """This rank's shard of a global MSM through the library's own RCCL communicator
         (comm_init first): local bucket method, ncclAllGather of the 160-byte partial sums,
         ordered fold on the device.  Returns the global sum as a (1, 20) numpy array."""
-        points, pp, n = self._prep(points, 20, np.uint64)
-        scalars, pk, _ = self._prep(scalars, 5, np.uint64)
         out = np.empty((1, 20), dtype=np.uint64)
-        self._call("zc_msm_sharded", pp, pk, n, out.ctypes.data)
+        self._msm("zc_msm_sharded", points, scalars, out.ctypes.data)
         return out
 
     def set_stream_dev(self, slot, stream_handle):
@@ -612,7 +409,7 @@ class MsmBases:
     def __init__(self, engine, points, window_bits=0):
         self.engine = engine
         self.id = 0
-        points, pp, n = engine._prep(points, 20, np.uint64)
+        points, pp, (n,) = engine._prep(points, 20, U64)
         self.n = n
         self.plan = engine.msm_fixed_plan(n, window_bits)
         out = C.c_uint64(0)
@@ -622,16 +419,9 @@ class MsmBases:
     def msm(self, scalars):
         if self.id == 0:
             raise _lib.ZerocafHipError("MsmBases: the table was closed")
-        shape = tuple(scalars.shape)
-        assert len(shape) in (2, 3) and shape[-2:] == (self.n, 5), (shape, self.n)
-        batch = 1 if len(shape) == 2 else shape[0]
-        if _is_torch(scalars):
-            assert scalars.is_contiguous() and scalars.element_size() == 8
-            self.engine._follow_torch_stream(scalars)
-            pk = scalars.data_ptr()
-        else:
-            scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
-            pk = scalars.ctypes.data
+        scalars, pk, lead = self.engine._prep(scalars, 5, U64, lead=len(scalars.shape) - 1)
+        assert len(lead) in (1, 2) and lead[-1] == self.n, (lead, self.n)
+        batch = 1 if len(lead) == 1 else lead[0]
         out = np.empty((batch, 20), dtype=np.uint64)
         self.engine._call("zc_msm_fixed", C.c_uint64(self.id), pk, batch, out.ctypes.data)
         return out

@@ -87,7 +87,7 @@ def test_release_library_carries_no_test_hooks_and_reads_its_knobs_once(lib):
                        "ZC_RING_SLOTS", "ZC_RISTRETTO_STRICT", "ZC_SCHED"], product
     hooks_only = sorted(x.decode() for x in strings(_lib.TEST_LIB_PATH) - strings(z.LIB_PATH))
     assert hooks_only == ["ZC_MSM_AFFINE_CHUNK", "ZC_MSM_FORK", "ZC_MSM_RUN", "ZC_MSM_RUN_EDGES", "ZC_MSM_SEG", "ZC_MSM_SORT_BIG", "ZC_MSM_SORT_G",
-                          "ZC_MSM_SORT_PACKED", "ZC_TEST_RING_POISON", "ZC_TEST_RING_SPINS", "ZC_TEST_STREAM_MIN_BYTES"], hooks_only
+                          "ZC_MSM_SORT_PACKED", "ZC_TEST_LAUNCH_FAIL", "ZC_TEST_RING_POISON", "ZC_TEST_RING_SPINS", "ZC_TEST_STREAM_MIN_BYTES"], hooks_only
     assert "PROBE" not in src                                # timing probes live in tools/debug/probes/*.patch
     assert "env_long(" in body and outside.count("env_long(") == 1                      # its definition only
 

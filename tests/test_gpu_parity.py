@@ -242,7 +242,7 @@ def _staged_inputs(n, seed, mod, edge, topbit, raw_every):
 @pytest.mark.parametrize("raw_every", [0, 8])
 def test_staged_mul_square_neg_kernels_every_output(eng, oracle, raw_every):
     """Beyond 256 MB per call Mul / Square / Neg move their 40-byte records through LDS (k_fe_mul_stream, k_fe_square_stream,
-    k_fe_neg_stream and the scalar forms; zerocaf_hip.hip: binop / unop).  EVERY output of device-resident batches of
+    k_fe_neg_stream and the scalar forms; zerocaf_hip.hip: binop / unop with a `Staged` kernel).  EVERY output of device-resident batches of
     2^22 + 3 (mul) and 2^23 - 5 (square, neg) elements -- ragged last workgroups -- against the oracle's Mul / Square / Neg
     (field.rs:250-262, :302-315, :217-240; scalar.rs:247-283): canonical operands with the edge set, then with every
     8th element a raw pattern at or above 2^T, which makes the wave take the two-pass product inside a staged block.

@@ -354,7 +354,30 @@ ZC_DI void store5(u64* __restrict__ p, const u64 (&l)[5])
     for (int i = 0; i < 5; i++) p[i] = l[i];
 }
 
-ZC_DI bool limbs52_all_zero(const u64 (&l)[5]) { return (l[0] | l[1] | l[2] | l[3] | l[4]) == 0; }
+// Is the element these five words hold 0 mod p?  The multiplier sees the value sum (l_i mod 2^52) 2^(52 i) mod p, so this is
+// the test that decides whether a row may enter a shared running product (fe_invert_chunk, ed_to_affine_chunk,
+// k_msm_prepare_affine): the words of k p (k = 1..255: five limbs below 2^52 each) or a word with only bits >= 2^52 set
+// are zero by value, and one such factor would zero every other row of its lane.  Same rule as fp_is_zero in the
+// one-element kernels.  Words without bits >= 2^52 and with a top word below 2^44 hold a value below 2^252 < p, which is
+// zero only if every word is: honest data never leaves that branch.  Any other pattern x < 2^260 is a multiple of p only
+// as k p with k = x >> 252 (k (p - 2^252) < 2^133), compared limb by limb.
+ZC_DI bool limbs52_zero_mod_p(const u64 (&l)[5])
+{
+    const u64 low = l[0] | l[1] | l[2] | l[3];
+    if (((low >> 52) | (l[4] >> 44)) == 0) return (low | l[4]) == 0;
+    const fe x = fe_from_limbs52(l);
+    const u32 k = x.v[8] >> 20;                            // bits 252..259
+    u64 t = 0;
+    u32 diff = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        t += (u64)k * ModP::N[i];
+        diff |= ((u32)t & M29) ^ x.v[i];
+        t >>= 29;
+    }
+    t += (u64)k * ModP::N[8];
+    return (diff | ((u32)t ^ x.v[8])) == 0;
+}
 
 // plain inverse of a register value (R-class, i.e. < 3N): acc -> acc^-1 mod N, no Montgomery factor
 ZC_DI fe fp_inverse_of_register(const fe& acc) { return fe_inverse_divsteps<FP>(fe_cond_sub_n<FP>(fe_cond_sub_n<FP>(acc))); }
@@ -378,7 +401,7 @@ ZC_DI void fe_invert_chunk(const u64* a, u64* out, uint8_t* ok, size_t n, size_t
     for (int j = 0; j < cnt; j++) {
         u64 l[5];
         load5(l, a + 5 * (lo + (size_t)j * stride));
-        const fe x = fe_select(limbs52_all_zero(l), neutral, fe_from_limbs52(l));
+        const fe x = fe_select(limbs52_zero_mod_p(l), neutral, fe_from_limbs52(l));
         u32* slot = reinterpret_cast<u32*>(out + 5 * (lo + (size_t)j * stride));
 #pragma unroll
         for (int w = 0; w < 9; w++) slot[w] = acc.v[w];    // acc_{j-1} (R mod p for j = 0)
@@ -388,7 +411,7 @@ ZC_DI void fe_invert_chunk(const u64* a, u64* out, uint8_t* ok, size_t n, size_t
     for (int j = cnt - 1; j >= 0; j--) {
         u64 l[5], r[5];
         load5(l, a + 5 * (lo + (size_t)j * stride));
-        const bool z = limbs52_all_zero(l);
+        const bool z = limbs52_zero_mod_p(l);
         const fe x = fe_select(z, neutral, fe_from_limbs52(l));
         const u32* slot = reinterpret_cast<const u32*>(out + 5 * (lo + (size_t)j * stride));
         fe pre;
@@ -1567,7 +1590,7 @@ ZC_DI bool ed_to_affine(fe& x, fe& y, const pt& p)
 // One lane's share of a batched affine conversion: Montgomery's trick over the Z coordinates of
 // up to `c` points lo, lo + stride, ... (as fe_invert_chunk: plain limbs are used as Montgomery residues, prefix
 // products wait in the first 36 bytes of each 80-byte output record), then x = X/Z, y = Y/Z.
-// Z = 0 (the reference's inverse panics) takes the neutral value and yields (0, 0) / ok = 0.
+// Z = 0 mod p (the reference's inverse panics; limbs52_zero_mod_p) takes the neutral value and yields (0, 0) / ok = 0.
 ZC_DI void ed_to_affine_chunk(const u64* p, u64* xy, uint8_t* ok, size_t n, size_t lo, size_t stride, int c)
 {
     const size_t avail = (n - lo + stride - 1) / stride;
@@ -1577,7 +1600,7 @@ ZC_DI void ed_to_affine_chunk(const u64* p, u64* xy, uint8_t* ok, size_t n, size
     for (int j = 0; j < cnt; j++) {
         u64 l[5];
         load5(l, p + 20 * (lo + (size_t)j * stride) + 10);
-        const fe z = fe_select(limbs52_all_zero(l), neutral, fe_from_limbs52(l));
+        const fe z = fe_select(limbs52_zero_mod_p(l), neutral, fe_from_limbs52(l));
         u32* slot = reinterpret_cast<u32*>(xy + 10 * (lo + (size_t)j * stride));
 #pragma unroll
         for (int w = 0; w < 9; w++) slot[w] = acc.v[w];
@@ -1589,7 +1612,7 @@ ZC_DI void ed_to_affine_chunk(const u64* p, u64* xy, uint8_t* ok, size_t n, size
         load5(lx, p + 20 * (lo + (size_t)j * stride));
         load5(ly, p + 20 * (lo + (size_t)j * stride) + 5);
         load5(lz, p + 20 * (lo + (size_t)j * stride) + 10);
-        const bool zero = limbs52_all_zero(lz);
+        const bool zero = limbs52_zero_mod_p(lz);
         const fe z = fe_select(zero, neutral, fe_from_limbs52(lz));
         const u32* slot = reinterpret_cast<const u32*>(xy + 10 * (lo + (size_t)j * stride));
         fe pre;

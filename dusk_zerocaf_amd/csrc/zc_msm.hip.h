@@ -137,7 +137,8 @@ ZC_KERNEL void k_msm_prepare(const u64* points, u32* cached, size_t n)
 // trick over their Z coordinates, the prefix products parked in the first 36 bytes of the records about to be
 // written (as ed_to_affine_chunk: plain limbs serve as Montgomery residues, fp_inverse_of_register returns the
 // plain inverse of the register value).  A wave whose points all have Z = 1 (decompressed or already affine
-// inputs) skips the inversion.  Z = 0 (no point of the curve) takes the neutral value: garbage in, garbage out.
+// inputs) skips the inversion.  Z = 0 mod p in any words (limbs52_zero_mod_p: no point of
+// the curve) takes the neutral value and stays out of the lane's running product: garbage in, garbage out for that point only.
 constexpr int MSM_AFF_WORDS = ZC_MSM_AFF_LIMBS ? 28 : 24;      // 32-bit words of a record as it is gathered (limb records: 27 used)
 constexpr int MSM_AFF_PIECES = MSM_AFF_WORDS / 4;              // ... in 16-byte pieces
 // All global traffic of the pass is coalesced: the workgroup's consecutive point records of a step come in through LDS with
@@ -232,7 +233,7 @@ void k_msm_prepare_affine(const u64* points, u32* recs, size_t n, int c, u32 rec
             u64 l[5];
             load5(l, sp + 20 * t + 10);
             all_one = all_one && l[0] == 1 && (l[1] | l[2] | l[3] | l[4]) == 0;
-            const fe z = fe_select(limbs52_all_zero(l), neutral, fe_from_limbs52(l));
+            const fe z = fe_select(limbs52_zero_mod_p(l), neutral, fe_from_limbs52(l));
 #pragma unroll
             for (int w = 0; w < 9; w++) spre[9 * t + w] = acc.v[w];
             acc = fp_mul(acc, z);
@@ -283,7 +284,7 @@ void k_msm_prepare_affine(const u64* points, u32* recs, size_t n, int c, u32 rec
             load5(lt, sp + 20 * t + 15);
             fe zi2 = fe_const<FP>(ModP::RR);                    // (1 / Z) R^2
             if (!skip) {
-                const fe z = fe_select(limbs52_all_zero(lz), neutral, fe_from_limbs52(lz));
+                const fe z = fe_select(limbs52_zero_mod_p(lz), neutral, fe_from_limbs52(lz));
                 fe pre;
 #pragma unroll
                 for (int w = 0; w < 9; w++) pre.v[w] = spre[9 * t + w];

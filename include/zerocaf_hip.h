@@ -32,6 +32,15 @@
  * panics or returns None for an individual element (inverse of 0, undecodable
  * point, scalar bytes > L-1), the optional `ok` mask gets 0 for that element (1
  * otherwise), the output element is zero/identity, and the call still succeeds.
+ * ZERO IS DECIDED BY VALUE.  A divisor of zc_fe_invert / zc_fe_div and a Z coordinate of zc_ed_to_affine are zero exactly
+ * when the value their five words hold, sum (w_i mod 2^52) 2^(52 i), is 0 mod p: five zero words, but also the limbs of
+ * p, 2p ... 255p, or a word with only bits >= 2^52 set.  Such a row gets out = 0 ((0, 0) for zc_ed_to_affine) and ok = 0
+ * in every launch form (any batch size, in place or not): it fails closed, where the reference -- whose assert compares
+ * limbs -- would go on to invert k p.  No row, however far outside the contract, changes the result of another row: the
+ * rows of a batch share inversions (Montgomery's trick), and a row that is zero by value is left out of the shared product.
+ * The affine normalisation of zc_msm / zc_msm_batch / zc_msm_bases_create follows the same rule (a point whose Z is 0 mod
+ * p is normalised with Z = 1: it is no point of the curve, garbage in, garbage out for its own term only), and under a zero
+ * scalar a point record contributes the identity whatever its words are, like the reference's `&P * &0`.
  * All functions are thread-safe per context (one context per thread or external
  * locking); there is NO CPU fallback: without a usable GPU every call fails with
  * ZC_ERR_NO_DEVICE.
@@ -113,9 +122,9 @@ int zc_fe_neg(zc_ctx *ctx, const uint64_t *a, uint64_t *out, size_t n);
 int zc_fe_mul(zc_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
 /* Square: field.rs:302-315 (square_internal :763-777) */
 int zc_fe_square(zc_ctx *ctx, const uint64_t *a, uint64_t *out, size_t n);
-/* inverse: field.rs:854-925 (panics on 0 -> ok[i] = 0, out = 0) */
+/* inverse: field.rs:854-925 (panics on 0 -> ok[i] = 0, out = 0; 0 by value mod p, see above) */
 int zc_fe_invert(zc_ctx *ctx, const uint64_t *a, uint64_t *out, uint8_t *ok, size_t n);
-/* Div: field.rs:277-300 (divide by 0 asserts -> ok = 0)   Half: :317-323   Pow: :325-355 (e: canonical limbs) */
+/* Div: field.rs:277-300 (divide by 0 mod p asserts -> ok = 0, out = 0)   Half: :317-323   Pow: :325-355 (e: canonical limbs) */
 int zc_fe_div(zc_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, uint8_t *ok, size_t n);
 int zc_fe_half(zc_ctx *ctx, const uint64_t *a, uint64_t *out, size_t n);
 int zc_fe_pow(zc_ctx *ctx, const uint64_t *a, const uint64_t *e, uint64_t *out, size_t n);
@@ -173,7 +182,7 @@ int zc_ed_scalar_mul(zc_ctx *ctx, const uint64_t *p, const uint64_t *k, uint64_t
  * mul_by_cofactor: :174-179                                                        */
 int zc_ed_mul_by_pow_2(zc_ctx *ctx, const uint64_t *p, uint64_t kexp, uint64_t *out, size_t n);
 int zc_ed_mul_by_cofactor(zc_ctx *ctx, const uint64_t *p, uint64_t *out, size_t n);
-/* AffinePoint::from: edwards.rs:1071-1092 (Z == 0 -> ok = 0)   ==: :360-370 */
+/* AffinePoint::from: edwards.rs:1071-1092 (Z == 0 mod p -> ok = 0, xy = (0, 0))   ==: :360-370 */
 int zc_ed_to_affine(zc_ctx *ctx, const uint64_t *p, uint64_t *xy_out, uint8_t *ok, size_t n);
 int zc_ed_eq(zc_ctx *ctx, const uint64_t *p, const uint64_t *q, uint8_t *eq_out, size_t n);
 /* compress: edwards.rs:613-629   decompress: :313-326 (None -> ok = 0, out = identity) */

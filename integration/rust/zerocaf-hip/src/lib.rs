@@ -356,7 +356,7 @@ impl HipBackend {
         Ok(unflat_fe(&self.un(ffi::zc_fe_half, &flat_fe(a), a.len(), 5)?))
     }
 
-    /// `a.inverse()` (`:854-925`); `None` where the reference panics (a = 0).
+    /// `a.inverse()` (`:854-925`); `None` where the reference panics (a = 0), decided by value: any limbs that are 0 mod p.
     pub fn fe_invert(&self, a: &[FieldElement]) -> Result<Vec<Option<FieldElement>>> {
         let (fa, n) = (flat_fe(a), a.len());
         let (mut out, mut ok) = (vec![0u64; n * 5], vec![0u8; n]);
@@ -562,7 +562,7 @@ impl HipBackend {
         Ok(unflat_ed(&self.un(ffi::zc_ed_mul_by_cofactor, &flat_ed(p), p.len(), 20)?))
     }
 
-    /// `AffinePoint::from(p)` (`:1071-1092`); `None` where Z = 0.
+    /// `AffinePoint::from(p)` (`:1071-1092`); `None` where Z = 0 mod p.
     pub fn ed_to_affine(&self, p: &[EdwardsPoint]) -> Result<Vec<Option<AffinePoint>>> {
         let (fp, n) = (flat_ed(p), p.len());
         let (mut xy, mut ok) = (vec![0u64; n * 10], vec![0u8; n]);

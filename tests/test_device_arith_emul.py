@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import hostile_rows as H
 from tests import vectors as V
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -406,3 +407,79 @@ def test_emul_extreme_operands(emul, oracle):
     assert np.array_equal(o3, oracle.proj_add(A3, B3))
     emul.emul_proj_double(p(A3), p(o3), C.c_size_t(n))
     assert np.array_equal(o3, oracle.proj_double(A3))
+
+
+# ------------------------------------------------------------------ hostile rows beside valid ones (tests/hostile_rows.py)
+HOSTILE_N = (63, 1007)
+HOSTILE_C = (2, 3, 5, 16, 64)
+_hostile_clean = {}
+
+
+def hostile_clean(oracle, n):
+    """Clean inputs of n rows and the oracle's answers, computed once and left unchanged."""
+    if n not in _hostile_clean:
+        den = V.limbs_array(V.rand_fe(n, V.SEED + 900 + n))
+        num = V.limbs_array(list(reversed(V.rand_fe(n, V.SEED + 901 + n))))
+        pts = V.base_multiples(oracle, n, V.SEED + 902 + n)
+        _hostile_clean[n] = (den, num, oracle.fe_invert(den), oracle.fe_div(num, den), pts, oracle.ed_to_affine(pts))
+    return _hostile_clean[n]
+
+
+def hostile_patterns(emul, pats):
+    """The bounds-checked build aborts on operands outside the lazy-reduction bounds, so it takes only the patterns whose
+    words are all below 2^52 (zeros, k p, p - 1, p + 1, 2^252, all limbs 2^52 - 1); the plain build takes every pattern."""
+    return [(name, w) for name, w in pats if H.narrow(w)] if emul.zc_checked else pats
+
+
+def check_rows(got, want, S, model_rows, tag):
+    """Clean rows: the oracle's limbs and ok.  Hostile rows: the answer for the value their words hold (0 mod p: out = 0, ok = 0)."""
+    keep = H.clean_mask(len(want[0]), S)
+    for g, w in zip(got, want):
+        assert np.array_equal(g[keep], w[keep]), (tag, np.flatnonzero(keep)[(g[keep].reshape(int(keep.sum()), -1) != w[keep].reshape(int(keep.sum()), -1)).any(axis=1)][:16])
+    for i, (out, ok) in model_rows:
+        assert got[0][i].tolist() == [int(x) for x in out] and got[1][i] == ok, (tag, i)
+
+
+@pytest.mark.parametrize("n", HOSTILE_N)
+def test_emul_hostile_divisors_leave_other_rows_alone(emul, oracle, n):
+    """fe_invert_chunk / its division form, both multipliers: a divisor that is 0 mod p without being five zero words (k p,
+    a word with only bits >= 2^52) must not enter the lane's running product -- every other row keeps the oracle's answer
+    with ok = 1; the row itself gets out = 0, ok = 0.  Hostile numerators change their own row only."""
+    den, num, want_inv, want_div, _, _ = hostile_clean(oracle, n)
+    pats = hostile_patterns(emul, H.fe_patterns())
+    assert sum(H.zero_by_value(w) and any(w) for _, w in pats) >= 4
+    out, ok = np.empty_like(den), np.empty(n, dtype=np.uint8)
+    for c in HOSTILE_C:
+        S = H.hostile_set(n, c)
+        for turn in range(len(pats)):
+            d2, n2 = den.copy(), num.copy()
+            planted = H.plant(d2, S, pats, turn)
+            for fn in (emul.emul_fe_invert_chunked, emul.emul_fe_invert_chunked_lone):
+                fn(p(d2), p(out), p(ok), C.c_size_t(n), c)
+                check_rows((out, ok), want_inv, S, [(i, H.fe_invert_model(w)) for i, _, w in planted], ("invert", c, turn))
+            H.plant(n2, S[::2], pats, turn + 5)                     # hostile numerators over hostile and (next) clean divisors
+            for fn in (emul.emul_fe_div_chunked, emul.emul_fe_div_chunked_lone):
+                fn(p(n2), p(d2), p(out), p(ok), C.c_size_t(n), c)
+                check_rows((out, ok), want_div, S, [(i, H.fe_div_model(n2[i], w)) for i, _, w in planted], ("div", c, turn))
+            n3 = num.copy()
+            T = [i + 1 for i in S[:-1]]                             # ... and over clean divisors: the row's own quotient changes, no other
+            if not set(T) & set(S):
+                H.plant(n3, T, pats, turn)
+                emul.emul_fe_div_chunked(p(n3), p(den), p(out), p(ok), C.c_size_t(n), c)
+                check_rows((out, ok), want_div, T, [(i, H.fe_div_model(n3[i], den[i])) for i in T], ("div numerators", c, turn))
+
+
+@pytest.mark.parametrize("n", HOSTILE_N)
+def test_emul_hostile_points_leave_other_affine_rows_alone(emul, oracle, n):
+    """ed_to_affine_chunk: a point whose Z is 0 mod p in any words, junk coordinates, saturated or all-ones records -- every
+    other point keeps the oracle's (x, y) and ok = 1; a Z of 0 mod p gives (0, 0), ok = 0."""
+    _, _, _, _, pts, want = hostile_clean(oracle, n)
+    pats = hostile_patterns(emul, H.point_patterns(pts[5]))
+    xy, ok = np.empty((n, 10), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+    for c in HOSTILE_C:
+        S = H.hostile_set(n, c)
+        for turn in range(len(pats)):
+            p2 = pts.copy()
+            planted = H.plant(p2, S, pats, turn)
+            emul.emul_ed_to_affine_chunked(p(p2), p(xy), p(ok), C.c_size_t(n), c)
+            check_rows((xy, ok), want, S, [(i, H.ed_to_affine_model(w)) for i, _, w in planted], ("to_affine", c, turn))

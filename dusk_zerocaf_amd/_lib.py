@@ -96,10 +96,17 @@ SIGNATURES = {
     "zc_comm_size": [C.POINTER(C.c_int)],
     "zc_ctx_set_stream_dev": [C.c_int, C.c_void_p, C.c_int],
 }
+# the scalar operations for protocols (reduction of arbitrary bytes, a*b + c, inversion mod L): bound like SIGNATURES
+SCALAR_EXT_SIGNATURES = {
+    "zc_sc_from_bytes_wide": [_u8p, _u64p, _n],
+    "zc_sc_from_bytes_mod_order": [_u8p, _u64p, _n],
+    "zc_sc_muladd": [_u64p, _u64p, _u64p, _u64p, _n],
+    "zc_sc_invert": [_u64p, _u64p, _u8p, _n],
+}
 CONTEXT_SYMBOLS = ["zc_ctx_create", "zc_ctx_destroy", "zc_ctx_device", "zc_ctx_device_count", "zc_ctx_set_stream", "zc_ctx_synchronize",
                    "zc_device_count", "zc_last_error", "zc_version", "zc_host_register", "zc_host_unregister",
                    "zc_comm_unique_id"]
-ALL_SYMBOLS = CONTEXT_SYMBOLS + list(SIGNATURES)
+ALL_SYMBOLS = CONTEXT_SYMBOLS + list(SIGNATURES) + list(SCALAR_EXT_SIGNATURES)
 
 _lib = None
 
@@ -145,7 +152,7 @@ def _bind(path: str) -> C.CDLL:
     lib.zc_host_register.argtypes = [C.c_void_p, C.c_size_t]
     lib.zc_host_unregister.argtypes = [C.c_void_p]
     lib.zc_comm_unique_id.argtypes = [C.c_void_p]
-    for name, sig in SIGNATURES.items():
+    for name, sig in list(SIGNATURES.items()) + list(SCALAR_EXT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = [_ctx] + sig
         fn.restype = C.c_int

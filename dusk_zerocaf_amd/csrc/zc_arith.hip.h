@@ -721,6 +721,58 @@ ZC_DI void fe_to_words256(u64 (&w)[4], const fe& c)
         w[j] = acc;
     }
 }
+// ---------------------------------------------------------------- scalars for protocols: wide reduction, multiply-add
+// v mod L for a 256-bit (WIDE = false: hi is not read) or 512-bit little-endian integer v = lo + 2^256 hi, canonical nine limbs.
+// Both halves go through the Montgomery multiplier, which takes any operand below 2^261 against a canonical constant
+// (a b < 2^256 N < 2 R N: result < 2N): lo R^2 / R = lo R and hi (2^256 R^2) / R = 2^256 hi R are the Montgomery forms of the
+// two summands -- the constant W256_RR absorbs the shift, so neither half needs a conversion of its own -- their lazy sum is
+// below 4N, and leaving the domain (fe_canon_from_mont) is the one reduction that canonicalises it.  162 + 54 multiply-adds for
+// 64 bytes, 81 + 54 for 32.  Not in the reference: Scalar::from_bytes_wide is unimplemented!() there (scalar.rs:469-474) and
+// from_bytes asserts s <= L - 1.
+template <bool WIDE>
+ZC_DI fe sc_reduce_words(const u64 (&lo)[4], const u64 (&hi)[4])
+{
+    fe s = mont_mul<ModL>(fe_from_words256(lo), fe_const<ModL>(ModL::RR));
+    if (WIDE) s = fe_add(s, mont_mul<ModL>(fe_from_words256(hi), fe_const<ModL>(ModL::W256_RR)));
+    return fe_canon_from_mont<ModL>(s);
+}
+// (val(a) val(b) + val(c)) mod L for plain five-word operands, canonical five-limb result; val(w) = sum (w_i mod 2^52) 2^(52 i).
+// Operands below 2^TOPBIT -- honest scalars -- take the one-pass product of fe_mulmod_limbs52 with c 2^PSHIFT added into the low
+// nine columns: X' = (a b + c) 2^S < 2^510, so the fold's bound HI < 2^TOPBIT still holds and the addition costs nine 64-bit
+// adds inside the column chain, nothing else.  A wave that holds any operand at or above 2^TOPBIT takes the Montgomery
+// multiplier for all three: (a R) b / R = a b below 1.75N and c (R mod N) / R = c below 1.5N (operands below 2^260), summed lazily.
+ZC_DI void sc_muladd_limbs52(u64 (&r)[5], const u64 (&xa)[5], const u64 (&xb)[5], const u64 (&xc)[5])
+{
+    typedef ModL F;
+    constexpr int TOP = F::TOPBIT - 208;
+    if (mulsq_wave_any((((xa[4] | xb[4] | xc[4]) & M52) >> TOP) != 0)) {
+        const fe p = mont_mul<F>(mont_to<F>(fe_from_limbs52(xa)), fe_from_limbs52(xb));
+        fe s = fe_add(p, mont_mul<F>(fe_from_limbs52(xc), fe_one_m<F>()));
+        fe_carry(s);
+#pragma unroll 1
+        for (int k = 0; k < 3; k++) s = fe_cond_sub_n<F>(s);                 // < 1.75N + 1.5N -> canonical
+        fe_to_limbs52(r, s);
+        return;
+    }
+    const fe a = fe_from_limbs52(xa), b = fe_from_limbs52_shl(xb, F::PSHIFT), c = fe_from_limbs52_shl(xc, F::PSHIFT);
+    u32 x[18];
+    u64 col = 0;
+#pragma unroll
+    for (int k = 0; k < 17; k++) {
+        if (k < 9) col += c.v[k];
+#pragma unroll
+        for (int i = 0; i < 9; i++)
+            if (k - i >= 0 && k - i < 9) {
+                col += (u64)a.v[i] * b.v[k - i];
+                ZC_PIN(col);
+            }
+        x[k] = (u32)col & M29;
+        col >>= 29;
+    }
+    x[17] = (u32)col;
+    fe_to_limbs52_shr(r, plain_fold_canon<F>(x), F::PSHIFT);
+}
+
 // ---------------------------------------------------------------- fixed exponentiation
 // a^e for a compile-time exponent e (wave-uniform control flow), left-to-right
 // binary.  Replaces the reference's data-dependent Pow / Savas-Koc / Tonelli

@@ -87,7 +87,9 @@ ZC_DI bool fp_eq(const fe& a, const fe& b) { return fp_is_zero(fp_sub(a, b)); }
 // a^-1 mod N through Bernstein-Yang division steps ("safegcd", the half-delta variant with its fixed
 // schedule): 20 rounds of 30 division steps on the low words of (f, g) = (N, a), each round followed by
 // one 2x2 integer matrix applied to the full-width (f, g) and, modulo N, to (d, e) = (0, 1); after 600
-// steps (590 suffice for 256-bit operands) g = 0, f = +-1 and d = +-a^-1.  Signed 30-bit limbs in
+// steps (590 suffice for 256-bit operands; the bound depends on the operands' length alone, so it holds for
+// the 250-bit scalar modulus L as it does for p, and fe_inverse_divsteps<ModL> runs the same 20 rounds)
+// g = 0, f = +-1 and d = +-a^-1.  Signed 30-bit limbs in
 // 32-bit registers; a round costs ~350 32-bit ALU instructions and ~110 multiplier-class ones (signed
 // 32 x 32 + 64 multiply-accumulates), i.e. an inversion costs about as much as 45 field
 // multiplications where the Fermat power a^(N-2) costs 290 -- and its dependent chain is as much
@@ -361,23 +363,27 @@ ZC_DI void store5(u64* __restrict__ p, const u64 (&l)[5])
 // one-element kernels.  Words without bits >= 2^52 and with a top word below 2^44 hold a value below 2^252 < p, which is
 // zero only if every word is: honest data never leaves that branch.  Any other pattern x < 2^260 is a multiple of p only
 // as k p with k = x >> 252 (k (p - 2^252) < 2^133), compared limb by limb.
-ZC_DI bool limbs52_zero_mod_p(const u64 (&l)[5])
+// The test is a template over the modulus N = 2^TOPBIT + c: for L = 2^249 + c' the honest branch is a top word below 2^41, and
+// the multiples k L with k = x >> 249 = 1..2047 (k c' < 2^135) are the ones that fit five 52-bit limbs (k_sc_invert*).
+template <class F>
+ZC_DI bool limbs52_zero_mod(const u64 (&l)[5])
 {
     const u64 low = l[0] | l[1] | l[2] | l[3];
-    if (((low >> 52) | (l[4] >> 44)) == 0) return (low | l[4]) == 0;
+    if (((low >> 52) | (l[4] >> (F::TOPBIT - 208))) == 0) return (low | l[4]) == 0;
     const fe x = fe_from_limbs52(l);
-    const u32 k = x.v[8] >> 20;                            // bits 252..259
+    const u32 k = x.v[8] >> F::TOPSHIFT;                   // bits TOPBIT..259
     u64 t = 0;
     u32 diff = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        t += (u64)k * ModP::N[i];
+        t += (u64)k * F::N[i];
         diff |= ((u32)t & M29) ^ x.v[i];
         t >>= 29;
     }
-    t += (u64)k * ModP::N[8];
+    t += (u64)k * F::N[8];
     return (diff | ((u32)t ^ x.v[8])) == 0;
 }
+ZC_DI bool limbs52_zero_mod_p(const u64 (&l)[5]) { return limbs52_zero_mod<ModP>(l); }
 
 // plain inverse of a register value (R-class, i.e. < 3N): acc -> acc^-1 mod N, no Montgomery factor
 ZC_DI fe fp_inverse_of_register(const fe& acc) { return fe_inverse_divsteps<FP>(fe_cond_sub_n<FP>(fe_cond_sub_n<FP>(acc))); }
@@ -390,45 +396,61 @@ ZC_DI fe fp_inverse_of_register(const fe& acc) { return fe_inverse_divsteps<FP>(
 // elements at 16 per lane: BASELINE configs[1]), where nothing hides the column-ordered multiplier's serial chain: 0.0877 ->
 // 0.0815 ms per 2^20 inversions; with more waves per SIMD the column-ordered form is the faster one (2^24: 0.994 against 1.004
 // ms), so the host picks per launch (profiles/r06_experiments/fe_invert_ab.md).
-template <bool ILP = false>
-ZC_DI void fe_invert_chunk(const u64* a, u64* out, uint8_t* ok, size_t n, size_t lo, size_t stride, int c, const u64* num = nullptr)
+// A template over the modulus: FP for zc_fe_invert / zc_fe_div (fe_invert_chunk below), ModL for zc_sc_invert.
+template <class F, bool ILP>
+ZC_DI void mod_invert_chunk(const u64* a, u64* out, uint8_t* ok, size_t n, size_t lo, size_t stride, int c, const u64* num = nullptr)
 {
-    auto fp_mul = [](const fe& x, const fe& y) { return ILP ? mont_mul_ilp<FP>(x, y) : mont_mul<FP>(x, y); };
+    auto fp_mul = [](const fe& x, const fe& y) { return ILP ? mont_mul_ilp<F>(x, y) : mont_mul<F>(x, y); };
     const size_t avail = (n - lo + stride - 1) / stride;
     const int cnt = (int)(avail < (size_t)c ? avail : (size_t)c);
-    const fe neutral = fe_one_m<FP>();
+    const fe neutral = fe_one_m<F>();
     fe acc = neutral;
     for (int j = 0; j < cnt; j++) {
         u64 l[5];
         load5(l, a + 5 * (lo + (size_t)j * stride));
-        const fe x = fe_select(limbs52_zero_mod_p(l), neutral, fe_from_limbs52(l));
+        const fe x = fe_select(limbs52_zero_mod<F>(l), neutral, fe_from_limbs52(l));
         u32* slot = reinterpret_cast<u32*>(out + 5 * (lo + (size_t)j * stride));
 #pragma unroll
-        for (int w = 0; w < 9; w++) slot[w] = acc.v[w];    // acc_{j-1} (R mod p for j = 0)
+        for (int w = 0; w < 9; w++) slot[w] = acc.v[w];    // acc_{j-1} (R mod N for j = 0)
         acc = fp_mul(acc, x);
     }
-    fe inv = fp_inverse_of_register(acc);                  // plain inverse of the register value
+    fe inv = fe_inverse_divsteps<F>(fe_cond_sub_n<F>(fe_cond_sub_n<F>(acc)));   // plain inverse of the register value (R-class)
     for (int j = cnt - 1; j >= 0; j--) {
         u64 l[5], r[5];
         load5(l, a + 5 * (lo + (size_t)j * stride));
-        const bool z = limbs52_zero_mod_p(l);
+        const bool z = limbs52_zero_mod<F>(l);
         const fe x = fe_select(z, neutral, fe_from_limbs52(l));
         const u32* slot = reinterpret_cast<const u32*>(out + 5 * (lo + (size_t)j * stride));
         fe pre;
 #pragma unroll
         for (int w = 0; w < 9; w++) pre.v[w] = slot[w];
-        fe res = fp_mul(inv, pre);                          // a_j^-1, plain, < 3p
+        fe res = fp_mul(inv, pre);                          // a_j^-1, plain, < 3N
         inv = fp_mul(inv, x);
         if (num) {
             u64 ln[5];
             load5(ln, num + 5 * (lo + (size_t)j * stride));
-            res = fp_mul(fe_from_limbs52(ln), mont_to<FP>(res));
+            res = fp_mul(fe_from_limbs52(ln), mont_to<F>(res));
         }
-        fe_to_limbs52(r, fe_cond_sub_n<FP>(fe_cond_sub_n<FP>(res)));
+        fe_to_limbs52(r, fe_cond_sub_n<F>(fe_cond_sub_n<F>(res)));
         if (z) r[0] = r[1] = r[2] = r[3] = r[4] = 0;
         store5(out + 5 * (lo + (size_t)j * stride), r);
         if (ok) ok[lo + (size_t)j * stride] = z ? 0 : 1;
     }
+}
+
+template <bool ILP = false>
+ZC_DI void fe_invert_chunk(const u64* a, u64* out, uint8_t* ok, size_t n, size_t lo, size_t stride, int c, const u64* num = nullptr)
+{
+    mod_invert_chunk<FP, ILP>(a, out, ok, n, lo, stride, c, num);
+}
+// val(l)^-1 mod L for one row, any five words: canonical limbs, or zero with *nz = false when the value is 0 mod L.  The value
+// is reduced by one Montgomery product with R mod L (l (R mod L) / R = l, below 1.5 L) and two subtractions; the division
+// steps take and return plain canonical values, so the row never enters the Montgomery domain.
+ZC_DI void sc_invert_limbs52(u64 (&r)[5], bool* nz, const u64 (&l)[5])
+{
+    const fe x = fe_cond_sub_n<ModL>(fe_cond_sub_n<ModL>(mont_mul<ModL>(fe_from_limbs52(l), fe_one_m<ModL>())));
+    *nz = !fe_is_zero_canon(x);
+    fe_to_limbs52(r, fe_inverse_divsteps<ModL>(x));                          // 0 -> 0
 }
 
 // a^e for a per-lane exponent e given as plain canonical limbs (Pow, field.rs:325-355):

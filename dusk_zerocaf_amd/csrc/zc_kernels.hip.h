@@ -488,6 +488,66 @@ ZC_KERNEL void k_sc_compute_naf(const u64* a, u32 width, int8_t* out, size_t n)
     }
 }
 
+// ------------------------------------------------------------------ scalars for protocols (not in the reference)
+// Hash-to-scalar, s = a b + c, a^-1 mod L: what a signature or a proof needs around the point calls.  Semantics by value,
+// val(w) = sum (w_i mod 2^52) 2^(52 i); every output is the canonical five limbs of the residue.
+// Byte records come in through 8-byte loads that promise no alignment (memcpy, not a cast to u64* as load_words256 does): a
+// caller's device pointer may sit at any byte, and global memory takes unaligned accesses.
+ZC_DI void load_words256_any(u64 (&w)[4], const uint8_t* p)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) __builtin_memcpy(&w[i], p + 8 * i, 8);
+}
+template <bool WIDE>
+ZC_DI void sc_from_bytes_body(const uint8_t* in, u64* out, size_t n)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    u64 lo[4], hi[4] = {0, 0, 0, 0}, l[5];
+    load_words256_any(lo, in + (WIDE ? 64 : 32) * i);
+    if (WIDE) load_words256_any(hi, in + 64 * i + 32);
+    fe_to_limbs52(l, sc_reduce_words<WIDE>(lo, hi));
+    store5(out + 5 * i, l);
+}
+ZC_KERNEL void k_sc_from_bytes_wide(const uint8_t* in, u64* out, size_t n) { sc_from_bytes_body<true>(in, out, n); }
+ZC_KERNEL void k_sc_from_bytes_mod_order(const uint8_t* in, u64* out, size_t n) { sc_from_bytes_body<false>(in, out, n); }
+// one product, one addition, one canonicalisation in registers: 160 bytes per row where zc_sc_mul + zc_sc_add move 240.
+// Every row is read before it is written, so `out` may be any of the inputs.
+ZC_KERNEL void k_sc_muladd(const u64* a, const u64* b, const u64* c, u64* out, size_t n)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    u64 x[5], y[5], z[5], r[5];
+    load5(x, a + 5 * i);
+    load5(y, b + 5 * i);
+    load5(z, c + 5 * i);
+    sc_muladd_limbs52(r, x, y, z);
+    store5(out + 5 * i, r);
+}
+// a^-1 mod L.  One element per lane (tiny batches, in place): one division-step inversion each.  Otherwise Montgomery's trick
+// per lane exactly as k_fe_invert_chunked does it for p (mod_invert_chunk<ModL>): 3 multiplications per element and one
+// inversion per lane, rows that are 0 mod L by value stay out of the running product.
+ZC_KERNEL void k_sc_invert(const u64* a, u64* out, uint8_t* ok, size_t n)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    u64 l[5], r[5];
+    load5(l, a + 5 * i);
+    bool nz;
+    sc_invert_limbs52(r, &nz, l);
+    store5(out + 5 * i, r);
+    if (ok) ok[i] = nz ? 1 : 0;
+}
+ZC_KERNEL void k_sc_invert_chunked(const u64* a, u64* out, uint8_t* ok, size_t n, int c)
+{
+    const size_t lanes = (n + (size_t)c - 1) / (size_t)c, g = gid();
+    if (g < lanes) mod_invert_chunk<ModL, false>(a, out, ok, n, g, lanes, c);
+}
+ZC_KERNEL void k_sc_invert_chunked_lone(const u64* a, u64* out, uint8_t* ok, size_t n, int c)
+{
+    const size_t lanes = (n + (size_t)c - 1) / (size_t)c, g = gid();
+    if (g < lanes) mod_invert_chunk<ModL, true>(a, out, ok, n, g, lanes, c);
+}
 
 // ------------------------------------------------------------------ point ops
 ZC_KERNEL void k_ed_add(const u64* p, const u64* q, u64* out, size_t n)

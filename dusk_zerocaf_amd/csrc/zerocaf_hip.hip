@@ -1473,6 +1473,19 @@ int zc_sc_compute_naf(zc_ctx* ctx, const uint64_t* a, unsigned width, int8_t* na
 }
 int zc_sc_from_bytes(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* ok, size_t n) { return from_bytes(ctx, in32, out, ok, 1, n); }
 int zc_sc_to_bytes(zc_ctx* ctx, const uint64_t* in, uint8_t* out32, size_t n) { return zc_fe_to_bytes(ctx, in, out32, n); }
+// ---- Scalar operations for protocols (not in the reference): reduction of 64 / 32 arbitrary bytes, a b + c, a^-1 mod L
+int zc_sc_from_bytes_wide(zc_ctx* ctx, const uint8_t* in64, uint64_t* out, size_t n) { return batched(ctx, n, false, plain(zc::k_sc_from_bytes_wide), ROWS(in64, 64), ROWS(out, 5)); }
+int zc_sc_from_bytes_mod_order(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, size_t n) { return batched(ctx, n, false, plain(zc::k_sc_from_bytes_mod_order), ROWS(in32, 32), ROWS(out, 5)); }
+int zc_sc_muladd(zc_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n)
+{
+    return batched(ctx, n, false, plain(zc::k_sc_muladd), ROWS(a, 5), ROWS(b, 5), ROWS(c, 5), ROWS(out, 5));
+}
+int zc_sc_invert(zc_ctx* ctx, const uint64_t* a, uint64_t* out, uint8_t* ok, size_t n)
+{
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* da, u64* dout, uint8_t* dok) {
+        return launch_shared_inversions(D, cnt, dout == da, zc::k_sc_invert, zc::k_sc_invert_chunked, zc::k_sc_invert_chunked_lone, da, dout, dok);
+    }, ROWS(a, 5), ROWS(out, 5), OPT_ROWS(ok, 1));
+}
 
 // ---- EdwardsPoint
 // staged records from 2^12 points on (below, a launch is a handful of workgroups and the barriers only cost)

@@ -237,6 +237,33 @@ struct Scalar {
         if (!ok) throw std::domain_error("scalar bytes > L - 1");            // scalar.rs:465 assert!
         return r;
     }
+    // Scalar operations for protocols (not in the reference): every input is accepted, results are canonical
+    static Scalar from_bytes_wide(const std::array<uint8_t, 64>& b)          // the 512-bit little-endian integer mod L
+    {
+        Scalar r;
+        Backend::check(zc_sc_from_bytes_wide(Backend::ctx(), b.data(), r.l.data(), 1), "zc_sc_from_bytes_wide");
+        return r;
+    }
+    static Scalar from_bytes_mod_order(const std::array<uint8_t, 32>& b)     // any 32 bytes mod L
+    {
+        Scalar r;
+        Backend::check(zc_sc_from_bytes_mod_order(Backend::ctx(), b.data(), r.l.data(), 1), "zc_sc_from_bytes_mod_order");
+        return r;
+    }
+    Scalar muladd(const Scalar& b, const Scalar& c) const                    // *this * b + c
+    {
+        Scalar r;
+        Backend::check(zc_sc_muladd(Backend::ctx(), l.data(), b.l.data(), c.l.data(), r.l.data(), 1), "zc_sc_muladd");
+        return r;
+    }
+    Scalar invert() const                                                    // a^-1 mod L; a = 0 mod L (by value) throws
+    {
+        Scalar r;
+        uint8_t ok = 0;
+        Backend::check(zc_sc_invert(Backend::ctx(), l.data(), r.l.data(), &ok, 1), "zc_sc_invert");
+        if (!ok) throw std::domain_error("scalar is 0 mod L: no inverse");
+        return r;
+    }
     std::array<uint8_t, 32> to_bytes() const
     {
         std::array<uint8_t, 32> b{};

@@ -356,6 +356,26 @@ int zc_ed_lincomb(zc_ctx *ctx, const uint64_t *points, const uint64_t *scalars, 
 int zc_ris_lincomb(zc_ctx *ctx, const uint8_t *in32, const uint64_t *scalars, size_t terms, const uint64_t *base_scalars,
                    uint8_t *out32, uint8_t *ok, size_t n);
 
+/* ---- scalar operations for protocols (additive to ABI 0.6): hash-to-scalar, s = r + c*x, a^-1 mod L ------------------------ */
+/* Not in the reference (its Scalar::from_bytes_wide is unimplemented!(), src/backend/u64/scalar.rs:469-474; it has no scalar
+ * inverse): the semantics are stated by value.  The value of five words is val(w) = sum (w_i mod 2^52) 2^(52 i) -- bits at or
+ * above 2^52 are ignored, a value has up to 260 bits -- and every output is the canonical five limbs (< 2^52 each, value < L)
+ * of the stated residue.  With zc_ris_mul_base_compress and zc_ris_lincomb a batched Schnorr sign / verify loop stays on the
+ * device; only the hash is the caller's.
+ *   zc_sc_from_bytes_wide       in64: n x 64 bytes, little-endian 512-bit integers v; out = v mod L.  Every input is taken,
+ *                               nothing is masked: the reduction of a 64-byte hash to a scalar.
+ *   zc_sc_from_bytes_mod_order  the same for n x 32 bytes: every 256-bit value is taken (zc_sc_from_bytes refuses > L - 1).
+ *   zc_sc_muladd                out = (val(a) val(b) + val(c)) mod L in one pass over memory; out may alias any input.
+ *   zc_sc_invert                out = val(a)^-1 mod L, ok = 1; a row whose value is 0 mod L -- five zero words, the limbs of
+ *                               L, 2L ... 2047L, words with only bits >= 2^52 set -- gets out = 0, ok = 0 in every launch form
+ *                               and stays out of the inversion its neighbours share (ZERO IS DECIDED BY VALUE, above).  ok may
+ *                               be NULL; out may alias a (one inversion per row then, as for zc_fe_invert).
+ * n == 0: ZC_OK, nothing written.  Buffers all in host memory or all on one device of the context, like every batched call. */
+int zc_sc_from_bytes_wide(zc_ctx *ctx, const uint8_t *in64, uint64_t *out, size_t n);
+int zc_sc_from_bytes_mod_order(zc_ctx *ctx, const uint8_t *in32, uint64_t *out, size_t n);
+int zc_sc_muladd(zc_ctx *ctx, const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t *out, size_t n);
+int zc_sc_invert(zc_ctx *ctx, const uint64_t *a, uint64_t *out, uint8_t *ok, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -510,6 +510,43 @@ impl HipBackend {
         Ok(unflat_b32(&out))
     }
 
+    // -------------------------------------------------------------- Scalar operations for protocols (not in the reference)
+    /// `v mod L` for little-endian 512-bit integers: the reduction of a 64-byte hash to a scalar. Every input is accepted.
+    pub fn sc_from_bytes_wide(&self, bytes: &[[u8; 64]]) -> Result<Vec<Scalar>> {
+        let flat: Vec<u8> = bytes.iter().flat_map(|b| b.iter().copied()).collect();
+        let n = bytes.len();
+        let mut out = vec![0u64; n * 5];
+        check(unsafe { ffi::zc_sc_from_bytes_wide(self.ctx, flat.as_ptr(), out.as_mut_ptr(), n) })?;
+        Ok(unflat_sc(&out))
+    }
+
+    /// `v mod L` for any 32 bytes: the companion of `sc_from_bytes` that refuses nothing.
+    pub fn sc_from_bytes_mod_order(&self, bytes: &[[u8; 32]]) -> Result<Vec<Scalar>> {
+        let flat: Vec<u8> = bytes.iter().flat_map(|b| b.iter().copied()).collect();
+        let n = bytes.len();
+        let mut out = vec![0u64; n * 5];
+        check(unsafe { ffi::zc_sc_from_bytes_mod_order(self.ctx, flat.as_ptr(), out.as_mut_ptr(), n) })?;
+        Ok(unflat_sc(&out))
+    }
+
+    /// `a * b + c mod L` in one pass (the `s = r + c * x` of a Schnorr signature).
+    pub fn sc_muladd(&self, a: &[Scalar], b: &[Scalar], c: &[Scalar]) -> Result<Vec<Scalar>> {
+        assert_eq!(a.len(), b.len());
+        assert_eq!(a.len(), c.len());
+        let (fa, fb, fc, n) = (flat_sc(a), flat_sc(b), flat_sc(c), a.len());
+        let mut out = vec![0u64; n * 5];
+        check(unsafe { ffi::zc_sc_muladd(self.ctx, fa.as_ptr(), fb.as_ptr(), fc.as_ptr(), out.as_mut_ptr(), n) })?;
+        Ok(unflat_sc(&out))
+    }
+
+    /// `a^-1 mod L`; `None` where the value is 0 mod L (decided by value: any limbs that are a multiple of L).
+    pub fn sc_invert(&self, a: &[Scalar]) -> Result<Vec<Option<Scalar>>> {
+        let (fa, n) = (flat_sc(a), a.len());
+        let (mut out, mut ok) = (vec![0u64; n * 5], vec![0u8; n]);
+        check(unsafe { ffi::zc_sc_invert(self.ctx, fa.as_ptr(), out.as_mut_ptr(), ok.as_mut_ptr(), n) })?;
+        Ok(masked(unflat_sc(&out), &ok))
+    }
+
     // -------------------------------------------------------------- EdwardsPoint (src/edwards.rs)
     /// `p + q` (`:465-501`), identical limbs.
     pub fn ed_add(&self, p: &[EdwardsPoint], q: &[EdwardsPoint]) -> Result<Vec<EdwardsPoint>> {

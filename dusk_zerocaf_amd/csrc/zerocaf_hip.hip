@@ -10,7 +10,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -141,43 +143,125 @@ Tuning tuning_from_env()
     return t;
 }
 
+// ---------------------------------------------------------------- owning handles
+// Whatever the library creates on a device is held by one of these move-only types and released by its destructor: a context,
+// a device slot or a fixed-base table that goes out of scope -- on whichever path -- takes its memory, streams and events along.
+
+// Device memory: pointer and capacity.
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : ptr_(std::exchange(o.ptr_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    ~DevBuf() { (void)reset(); }
+    // At least `need` bytes: nothing to do when the capacity is enough; otherwise the block is freed (its contents go) and
+    // max(need, 1 MiB) allocated.  A failed allocation leaves the buffer empty.
+    int grow(size_t need) { return cap_ >= need ? ZC_OK : alloc(std::max(need, (size_t)1 << 20), "hipMalloc(scratch)"); }
+    // Exactly `bytes`, for what never changes its size; `what` names the allocation in the message of a failure.
+    int alloc(size_t bytes, const char* what)
+    {
+        HIP_TRY(reset());
+        const hipError_t e = hipMalloc(&ptr_, bytes);
+        if (e != hipSuccess) return ptr_ = nullptr, fail(ZC_ERR_NOMEM, what, e);
+        cap_ = bytes;
+        return ZC_OK;
+    }
+    hipError_t reset()
+    {
+        const hipError_t e = ptr_ ? hipFree(ptr_) : hipSuccess;
+        ptr_ = nullptr;
+        cap_ = 0;
+        return e;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(ptr_); }
+    explicit operator bool() const { return ptr_ != nullptr; }
+
+  private:
+    void* ptr_ = nullptr;
+    size_t cap_ = 0;
+};
+// A HIP handle with the call that releases it; converts to the plain handle wherever HIP takes one.
+template <class H, hipError_t (*Release)(H)>
+class Handle {
+  public:
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    ~Handle() { if (h_) (void)Release(h_); }
+    operator H() const { return h_; }
+    H* put() { return &h_; }            // where the creating HIP call stores it (an empty handle only)
+
+  private:
+    H h_ = nullptr;
+};
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using PinnedMem = Handle<void*, hipHostFree>;
+
+// One device slot of a context.  Created in place (zc_ctx_create) and never moved afterwards: pointers to it are taken everywhere.
 struct DevState {
     int device = 0;
     Tuning tune;                        // the context's knobs (a copy per device slot)
     int cus = 256;                      // compute units (multiProcessorCount)
-    hipStream_t stream = nullptr;       // owned
-    hipStream_t borrowed = nullptr;     // set by zc_ctx_set_stream (device 0 only)
+    Stream stream;                      // owned
+    hipStream_t borrowed = nullptr;     // set by zc_ctx_set_stream (device 0 only): the caller's, not released here
     bool use_borrowed = false;
-    hipStream_t copy_in = nullptr;      // host batches: upload / download streams of the chunk pipeline
-    hipStream_t copy_out = nullptr;
-    std::vector<hipEvent_t> ev;         // 2 per chunk: inputs landed, kernel done
-    void* scratch[MAX_ARGS] = {};
-    size_t scratch_bytes[MAX_ARGS] = {};
-    void* tmp[2] = {};                  // zc_msm partials
-    size_t tmp_bytes[2] = {};
-    void* bal = nullptr;                // lane balancing: 1024 u32 bins + n u32 indices
-    size_t bal_bytes = 0;
-    void* msm = nullptr;                // bucket-method workspace (zc_msm)
-    size_t msm_bytes = 0;
-    void* fast = nullptr;               // windowed-core tables: ring of wave slots, 256 MB (zc_kernels.hip.h)
-    size_t fast_bytes = 0;
-    void* ring = nullptr;               // tickets and slot flags of the table ring (+ the device address of the error word)
-    size_t ring_bytes = 0;
-    volatile zc::u32* ring_err = nullptr;   // the ring's error word: pinned host memory, written by a wave that gave up
-    void* base_table = nullptr;         // comb table of the basepoint: 33 x 128 cached affine points
-    size_t base_bytes = 0;
-    void* odd_table = nullptr;          // (2j - 1) B, j = 1..125, cached affine: the w-NAF's odd multiples
-    size_t odd_bytes = 0;
-    void* part = nullptr;               // MSM exchange: gathered per-rank / per-device partials + the folded result
-    size_t part_bytes = 0;
-    hipEvent_t ev_order = nullptr;      // orders work across a stream switch / across devices
-    hipStream_t aux = nullptr;          // MSM: the point normalisation runs beside the key sort (other priority than `stream`:
+    Stream copy_in, copy_out;           // host batches: upload / download streams of the chunk pipeline
+    std::vector<Event> ev;              // 2 per chunk: inputs landed, kernel done
+    DevBuf scratch[MAX_ARGS];           // staging areas of host batches, one per buffer of the call
+    DevBuf bal;                         // lane balancing: 1024 u32 bins + n u32 indices
+    DevBuf msm;                         // the MSM workspace: bucket method, or the products and folds of a small shard / batch
+    DevBuf fast;                        // windowed-core tables: ring of wave slots, 256 MB (zc_kernels.hip.h)
+    DevBuf ring;                        // tickets and slot flags of the table ring (+ the device address of the error word)
+    PinnedMem ring_err;                 // the ring's error word: pinned host memory, written by a wave that gave up
+    DevBuf base_table;                  // comb table of the basepoint: 33 x 128 cached affine points
+    DevBuf odd_table;                   // (2j - 1) B, j = 1..125, cached affine: the w-NAF's odd multiples
+    DevBuf part;                        // MSM exchange: gathered per-rank / per-device partials + the folded result
+    Event ev_order;                     // orders work across a stream switch / across devices
+    Stream aux;                         // MSM: the point normalisation runs beside the key sort (other priority than `stream`:
                                         // two streams of one priority share a hardware queue here and run one after the other)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t grp = nullptr;          // MSM window groups: the chains of the groups above the lowest one, one after the other (highest priority)
-    hipEvent_t ev_grp_go[3] = {}, ev_grp_done[3] = {};   // group g's bucket sums are enqueued / its chain is through
-    unsigned long long staged_launches = 0;   // element-wise / point launches that took the LDS-staged kernel (read by the test build's zc_test_staged_launches)
-    hipStream_t s() const { return use_borrowed ? borrowed : stream; }
+    Event ev_fork, ev_join;
+    Stream grp;                         // MSM window groups: the chains of the groups above the lowest one, one after the other (highest priority)
+    Event ev_grp_go[3], ev_grp_done[3];   // group g's bucket sums are enqueued / its chain is through
+#ifdef ZC_TEST_HOOKS
+    unsigned long long staged_launches = 0;   // element-wise / point launches that took the LDS-staged kernel (zc_test_staged_launches)
+#endif
+
+    DevState() = default;
+    DevState(DevState&&) = default;
+    // Work that may still use the slot's memory ends before the members release it.
+    ~DevState()
+    {
+        if (!stream) return;            // never opened, or moved from: the members hold nothing
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(s());
+        if (grp) (void)hipStreamSynchronize(grp);
+    }
+    // The streams and events of a slot on HIP device `id`, which becomes the current device.
+    hipError_t open(int id, const Tuning& knobs)
+    {
+        device = id;
+        tune = knobs;
+        const auto event = [](Event& ev) { return hipEventCreateWithFlags(ev.put(), hipEventDisableTiming); };
+        int lo_p = 0, hi_p = 0;                                         // lowest, highest (numerically smaller = higher)
+        hipError_t e = hipSetDevice(id);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, id);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(stream.put(), hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(copy_in.put(), hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(copy_out.put(), hipStreamNonBlocking);
+        if (e == hipSuccess) e = event(ev_order);
+        if (e == hipSuccess) (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(aux.put(), hipStreamNonBlocking, lo_p);
+        if (e == hipSuccess) e = event(ev_fork);
+        if (e == hipSuccess) e = event(ev_join);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(grp.put(), hipStreamNonBlocking, ZC_MSM_TAIL_PRIO ? hi_p : 0);
+        for (int g = 0; g < 3 && e == hipSuccess; g++) {
+            e = event(ev_grp_go[g]);
+            if (e == hipSuccess) e = event(ev_grp_done[g]);
+        }
+        return e;
+    }
+    hipStream_t s() const { return use_borrowed ? borrowed : (hipStream_t)stream; }
+    volatile zc::u32* ring_error() const { return static_cast<volatile zc::u32*>((void*)ring_err); }
 };
 
 // librccl entry points (resolved at zc_comm_init; the library has no link-time dependency on RCCL)
@@ -194,8 +278,8 @@ struct RcclApi {
 // A fixed-base MSM table (zc_msm_bases_create): W windows of n affine records, its own allocation on device slot `slot`.
 struct MsmBases {
     int slot = 0;
-    void* recs = nullptr;
-    size_t n = 0, bytes = 0;
+    DevBuf recs;
+    size_t n = 0;
     int c = 0, W = 0;
 };
 std::atomic<uint64_t> g_next_bases_id{1};   // table ids: nonzero, process-wide, never reused
@@ -203,9 +287,10 @@ std::atomic<uint64_t> g_next_bases_id{1};   // table ids: nonzero, process-wide,
 }  // namespace
 
 struct zc_ctx {
-    std::vector<DevState> devs;
+    std::map<uint64_t, MsmBases> bases;   // live fixed-base tables by id (ids come from one process-wide counter: never reused);
+                                          // declared before the slots, so released after every slot has drained its streams
+    std::vector<DevState> devs;           // reserved at creation: the slots never move
     std::mutex mu;
-    std::map<uint64_t, MsmBases> bases;   // live fixed-base tables by id (ids come from one process-wide counter: never reused)
     ncclComm_t comm = nullptr;          // zc_comm_init: one rank per process, device 0 of the context
     int rank = 0, world = 1;
 };
@@ -241,17 +326,34 @@ int residency_of(const void* p, Residency* res, int* device)
     return ZC_OK;
 }
 
-int ensure(void** buf, size_t* have, size_t need)
+// Where the buffers of one call live (null pointers are skipped, one query per buffer): *owner = the device slot of the context that
+// holds them all, null = all of them host memory; anything else is ZC_ERR_MIXED_MEM.  `who` prefixes the messages ("" or "zc_...: ").
+int owner_of(zc_ctx* ctx, const void* const* ptrs, size_t nptrs, const char* who, DevState** owner)
 {
-    if (*have >= need) return ZC_OK;
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    size_t want = std::max(need, (size_t)1 << 20);
-    hipError_t e = hipMalloc(buf, want);
-    if (e != hipSuccess) return fail(ZC_ERR_NOMEM, "hipMalloc(scratch)", e);
-    *have = want;
+    int on_device = 0, on_host = 0, device = -1;
+    for (size_t i = 0; i < nptrs; i++) {
+        if (!ptrs[i]) continue;
+        Residency r;
+        int d = -1;
+        residency_of(ptrs[i], &r, &d);
+        if (r != RES_DEVICE) {
+            on_host++;
+            continue;
+        }
+        if (on_device++ && d != device) return failf(ZC_ERR_MIXED_MEM, "%sbuffers on different devices", who);
+        device = d;
+    }
+    if (on_device && on_host) return failf(ZC_ERR_MIXED_MEM, "%shost and device buffers mixed in one call", who);
+    *owner = nullptr;
+    if (!on_device) return ZC_OK;
+    for (auto& d : ctx->devs)
+        if (d.device == device && !*owner) *owner = &d;
+    if (!*owner) return failf(ZC_ERR_MIXED_MEM, "%sdevice buffers do not belong to a device of this context", who);
     return ZC_OK;
+}
+inline int owner_of(zc_ctx* ctx, std::initializer_list<const void*> ptrs, const char* who, DevState** owner)
+{
+    return owner_of(ctx, ptrs.begin(), ptrs.size(), who, owner);
 }
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + zc::ZC_BLOCK - 1) / zc::ZC_BLOCK); }
@@ -298,34 +400,19 @@ int run_batched(zc_ctx* ctx, const Arg* args, int nargs, size_t n, Launch&& laun
     };
     std::lock_guard<std::mutex> lock(ctx->mu);
 
-    int ndevptr = 0, nhostptr = 0, dev_of_ptrs = -1;
-    for (int a = 0; a < nargs; a++) {
-        if (!args[a].ptr) continue;
-        Residency r;
-        int d = -1;
-        residency_of(args[a].ptr, &r, &d);
-        if (r == RES_DEVICE) {
-            ndevptr++;
-            if (dev_of_ptrs >= 0 && d != dev_of_ptrs) return fail(ZC_ERR_MIXED_MEM, "buffers on different devices");
-            dev_of_ptrs = d;
-        } else {
-            nhostptr++;
-        }
-    }
-    if (ndevptr && nhostptr) return fail(ZC_ERR_MIXED_MEM, "host and device buffers mixed in one call");
+    const void* ptrs[MAX_ARGS];
+    for (int a = 0; a < nargs; a++) ptrs[a] = args[a].ptr;
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, ptrs, (size_t)nargs, "", &owner)) return rc;
 
-    if (ndevptr) {
+    if (owner) {
         // in-place on the device that owns the buffers, asynchronous on the context stream
-        DevState* ds = nullptr;
-        for (auto& d : ctx->devs)
-            if (d.device == dev_of_ptrs) ds = &d;
-        if (!ds) return fail(ZC_ERR_MIXED_MEM, "device buffers do not belong to a device of this context");
-        if (int rc = ring_check(*ds)) return rc;            // an asynchronous failure of an earlier call surfaces here
-        HIP_TRY(hipSetDevice(ds->device));
+        if (int rc = ring_check(*owner)) return rc;         // an asynchronous failure of an earlier call surfaces here
+        HIP_TRY(hipSetDevice(owner->device));
         void* dptr[MAX_ARGS];
         for (int a = 0; a < nargs; a++) dptr[a] = const_cast<void*>(args[a].ptr);
         long calls = 0;
-        if (int rc = launch_counted(dptr, n, *ds, calls)) return rc;
+        if (int rc = launch_counted(dptr, n, *owner, calls)) return rc;
         HIP_TRY(hipGetLastError());
         return ZC_OK;
     }
@@ -352,14 +439,13 @@ int run_batched(zc_ctx* ctx, const Arg* args, int nargs, size_t n, Launch&& laun
             void* base[MAX_ARGS] = {};
             for (int a = 0; a < nargs; a++) {
                 if (!args[a].ptr) continue;
-                int rc = ensure(&ds.scratch[a], &ds.scratch_bytes[a], args[a].elt_bytes * total);
-                if (rc) return rc;
-                base[a] = ds.scratch[a];
+                if (int rc = ds.scratch[a].grow(args[a].elt_bytes * total)) return rc;
+                base[a] = ds.scratch[a].as<void>();
             }
             while (ds.ev.size() < 2 * nchunks) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                ds.ev.push_back(e);
+                Event e;
+                HIP_TRY(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+                ds.ev.push_back(std::move(e));
             }
             // chunk j: upload on copy_in, kernel on the context stream, download on copy_out
             auto upload_and_launch = [&](size_t j) -> int {
@@ -500,13 +586,21 @@ inline size_t staged_min(const DevState& D, size_t min_bytes)
     (void)D;
     return min_bytes;
 }
+// (the test build counts the launches that took a staged kernel: zc_test_staged_launches)
+inline void count_staged(DevState& D, bool staged)
+{
+#ifdef ZC_TEST_HOOKS
+    D.staged_launches += staged ? 1 : 0;
+#endif
+    (void)D, (void)staged;
+}
 // out = a op b / out = op a over rows of `per` limbs
 int binop(zc_ctx* ctx, kbin_t k, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, size_t per, Staged<kbin_t> st = {})
 {
     return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, const u64* db, u64* dout) {
         const bool staged = st.kernel && cnt * sizeof(u64) * per * 3 > staged_min(D, st.min_bytes) && aligned16(da) && aligned16(db) && aligned16(dout);
         const unsigned blk = staged ? st.block : (unsigned)zc::ZC_BLOCK;
-        D.staged_launches += staged ? 1 : 0;
+        count_staged(D, staged);
         hipLaunchKernelGGL(staged ? st.kernel : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), da, db, dout, cnt);
         return ZC_OK;
     }, ROWS(a, per), ROWS(b, per), ROWS(out, per));
@@ -516,7 +610,7 @@ int unop(zc_ctx* ctx, kun_t k, const uint64_t* a, uint64_t* out, size_t n, size_
     return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) {
         const bool staged = st.kernel && cnt * sizeof(u64) * per * 2 > staged_min(D, st.min_bytes) && aligned16(da) && aligned16(dout);
         const unsigned blk = staged ? st.block : (unsigned)zc::ZC_BLOCK;
-        D.staged_launches += staged ? 1 : 0;
+        count_staged(D, staged);
         hipLaunchKernelGGL(staged ? st.kernel : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), da, dout, cnt);
         return ZC_OK;
     }, ROWS(a, per), ROWS(out, per));
@@ -532,8 +626,8 @@ const zc::u32* balance_index(DevState& D, const u64* k, size_t cnt, zc::u32** co
 {
     if (cnt < BALANCE_MIN_N || cnt > 0xFFFFFFFFull) return nullptr;
     const size_t need = (zc::ZC_COST_BINS + BAL_COUNTERS + cnt) * sizeof(zc::u32);
-    if (ensure(&D.bal, &D.bal_bytes, need) != ZC_OK) return nullptr;
-    zc::u32* hist = (zc::u32*)D.bal;
+    if (D.bal.grow(need) != ZC_OK) return nullptr;
+    zc::u32* hist = D.bal.as<zc::u32>();
     zc::u32* idx = hist + zc::ZC_COST_BINS + BAL_COUNTERS;
     if (hipMemsetAsync(hist, 0, (zc::ZC_COST_BINS + BAL_COUNTERS) * sizeof(zc::u32), D.s()) != hipSuccess) return nullptr;
     hipLaunchKernelGGL(zc::k_sm_cost_hist, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), k, hist, cnt);
@@ -580,34 +674,28 @@ template <class L>
 int fast_ring(DevState& D, size_t cnt, L&& launch, size_t slot_units = 1)
 {
     const size_t units_per_xcd = ring_units_per_xcd(slot_units);
-    int rc = ensure(&D.fast, &D.fast_bytes, zc::RING_TABLE_BYTES / zc::RING_SLOTS * units_per_xcd);
-    if (rc) return rc;
+    if (int rc = D.fast.grow(zc::RING_TABLE_BYTES / zc::RING_SLOTS * units_per_xcd)) return rc;
     if (!D.ring) {
         // The error word lives in pinned HOST memory the device can write (a wave that gives up stores through the
         // address parked behind the ring state): the host reads it at every entry point without any synchronisation.
         if (!D.ring_err) {
-            void* h = nullptr;
             // coherent (fine-grained) so that the host sees the store while kernels run whatever HIP_HOST_COHERENT says;
             // portable so that every device slot of a multi-device context may map it
-            hipError_t e = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable);
+            hipError_t e = hipHostMalloc(D.ring_err.put(), 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable);
             if (e != hipSuccess) return fail(ZC_ERR_NOMEM, "hipHostMalloc(ring error word)", e);
-            D.ring_err = (volatile zc::u32*)h;
-            *D.ring_err = 0;
+            *D.ring_error() = 0;
         }
-        // the ring state is published (D.ring) only once the error word's address sits behind it: a failure on the way
-        // leaves D.ring null and the next call starts over -- a wave never reads an unset address
-        void* ring = nullptr;
-        HIP_TRY(hipMalloc(&ring, zc::RING_ALLOC_WORDS * sizeof(zc::u32)));
+        // the ring state stays (D.ring) only once the error word's address sits behind it: a failure on the way
+        // leaves D.ring empty and the next call starts over -- a wave never reads an unset address
+        if (int rc = D.ring.alloc(zc::RING_ALLOC_WORDS * sizeof(zc::u32), "hipMalloc(ring state)")) return rc;
         void* dev_view = nullptr;
         hipError_t e = hipHostGetDevicePointer(&dev_view, (void*)D.ring_err, 0);
         const u64 addr = (u64)(uintptr_t)dev_view;
-        if (e == hipSuccess) e = hipMemcpy((zc::u32*)ring + zc::RING_ERR_WORD, &addr, sizeof addr, hipMemcpyHostToDevice);   // once per device slot
+        if (e == hipSuccess) e = hipMemcpy(D.ring.as<zc::u32>() + zc::RING_ERR_WORD, &addr, sizeof addr, hipMemcpyHostToDevice);   // once per device slot
         if (e != hipSuccess) {
-            (void)hipFree(ring);
+            (void)D.ring.reset();
             return fail(ZC_ERR_HIP, "windowed core: ring state setup", e);
         }
-        D.ring = ring;
-        D.ring_bytes = zc::RING_ALLOC_WORDS * sizeof(zc::u32);
     }
     // a launch hands out fewer than 2^19 generations of its slots (the 19-bit field of the word ring_acquire parks)
     const zc::u32 slots = std::min(D.tune.ring_slots ? (zc::u32)D.tune.ring_slots : zc::RING_SLOTS, (zc::u32)(units_per_xcd / slot_units));
@@ -617,11 +705,11 @@ int fast_ring(DevState& D, size_t cnt, L&& launch, size_t slot_units = 1)
 #endif
     const size_t max_launch = std::min(FAST_MAX_LAUNCH, (size_t)slots << 24);
     for (size_t off = 0; off < cnt; off += max_launch) {
-        HIP_TRY(hipMemsetAsync(D.ring, 0, zc::RING_STATE_WORDS * sizeof(zc::u32), D.s()));
-        launch((zc::u32*)D.fast, (zc::u32*)D.ring, slots_arg, off, std::min(max_launch, cnt - off));
+        HIP_TRY(hipMemsetAsync(D.ring.as<void>(), 0, zc::RING_STATE_WORDS * sizeof(zc::u32), D.s()));
+        launch(D.fast.as<zc::u32>(), D.ring.as<zc::u32>(), slots_arg, off, std::min(max_launch, cnt - off));
     }
 #ifdef ZC_TEST_HOOKS
-    if (D.tune.test_ring_poison) *D.ring_err = 1;            // pretend a wave gave up (exercises the report-and-recover path)
+    if (D.tune.test_ring_poison) *D.ring_error() = 1;            // pretend a wave gave up (exercises the report-and-recover path)
 #endif
     return ZC_OK;
 }
@@ -631,8 +719,9 @@ int fast_ring(DevState& D, size_t cnt, L&& launch, size_t slot_units = 1)
 // Reported once (ZC_ERR_HIP), then cleared: the context stays usable.
 int ring_check(DevState& D)
 {
-    if (!D.ring_err || *D.ring_err == 0) return ZC_OK;
-    *D.ring_err = 0;
+    volatile zc::u32* const err = D.ring_error();
+    if (!err || *err == 0) return ZC_OK;
+    *err = 0;
     return fail(ZC_ERR_HIP, "windowed core: a wave timed out waiting for its table slot; the rows it owned hold poison (all ones) -- "
                             "the outputs of the last windowed-core calls on this device are not valid");
 }
@@ -700,8 +789,8 @@ struct MsmWorkspace {
 int msm_workspace(DevState& D, const MsmBucketPlan& p, size_t cached_points, size_t out_points, MsmWorkspace* ws, bool sort_only = false)
 {
     const zc::MsmLayout l = zc::msm_workspace_layout(p, cached_points, out_points, sort_only);
-    if (int rc = ensure(&D.msm, &D.msm_bytes, l.total)) return rc;
-    char* const b = (char*)D.msm;
+    if (int rc = D.msm.grow(l.total)) return rc;
+    char* const b = D.msm.as<char>();
     *ws = MsmWorkspace{(zc::u32*)(b + l.digits), (uint2*)(b + l.pairs_a), p.sort.passes == 1 ? nullptr : (void*)(b + l.pairs_b),
                        (zc::u32*)(b + l.sort_table), (zc::u32*)(b + l.sort_sums), (zc::u32*)(b + l.cached), (zc::u32*)(b + l.buckets),
                        (uint8_t*)(b + l.present), {(zc::u32*)(b + l.ekeys[0]), (zc::u32*)(b + l.ekeys[1])},
@@ -916,13 +1005,14 @@ int msm_reduce_windows(DevState& D, const MsmReduceBufs& rb, const MsmReduceArgs
 int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u64** result)
 {
     if (cnt < zc::MSM_BUCKET_MIN_N) {
-        // small shard: n scalar-muls, then pairwise folds
-        int rc = ensure(&D.tmp[0], &D.tmp_bytes[0], cnt * 160);
-        if (rc) return rc;
-        rc = ensure(&D.tmp[1], &D.tmp_bytes[1], ((cnt + 1) / 2) * 160 + 256);
-        if (rc) return rc;
-        hipLaunchKernelGGL(strict_kernel_for(cnt), dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dP, dK, (size_t)5, (u64*)D.tmp[0], cnt);
-        *result = fold_all(D, (u64*)D.tmp[0], (u64*)D.tmp[1], cnt);
+        // small shard: n scalar-muls, then pairwise folds, in two buffers of the workspace: the products, and the other side of the
+        // folds' ping-pong (laid out as msm_batch_on_device lays out its own)
+        const size_t prod_bytes = (cnt * 160 + 255) & ~(size_t)255;
+        if (int rc = D.msm.grow(prod_bytes + ((cnt + 1) / 2) * 160 + 256)) return rc;
+        u64* const prod = D.msm.as<u64>();
+        u64* const half = (u64*)(D.msm.as<char>() + prod_bytes);
+        hipLaunchKernelGGL(strict_kernel_for(cnt), dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dP, dK, (size_t)5, prod, cnt);
+        *result = fold_all(D, prod, half, cnt);
         HIP_TRY(hipGetLastError());
         return ZC_OK;
     }
@@ -1078,26 +1168,6 @@ int rccl_fail(const char* what, ncclResult_t r)
         if (r_ != ncclSuccess) return rccl_fail(#expr, r_);    \
     } while (0)
 
-DevState* dev_state_of(zc_ctx* ctx, int device)
-{
-    for (auto& d : ctx->devs)
-        if (d.device == device) return &d;
-    return nullptr;
-}
-
-// Where the two input arrays of an MSM live: *owner = the device slot of the context that holds both, null = host memory.
-// `who` prefixes the messages ("" or "zc_...: ").
-int msm_inputs_owner(zc_ctx* ctx, const void* points, const void* scalars, const char* who, DevState** owner)
-{
-    Residency rp, rk;
-    int dp = -1, dk = -1;
-    residency_of(points, &rp, &dp);
-    residency_of(scalars, &rk, &dk);
-    if (rp != rk || (rp == RES_DEVICE && dp != dk)) return failf(ZC_ERR_MIXED_MEM, "%spoints/scalars residency differs", who);
-    *owner = rp == RES_DEVICE ? dev_state_of(ctx, dp) : nullptr;
-    if (rp == RES_DEVICE && !*owner) return failf(ZC_ERR_MIXED_MEM, "%sdevice buffers do not belong to a device of this context", who);
-    return ZC_OK;
-}
 // The inputs of an MSM call to device D, which becomes the current device; an asynchronous failure of an earlier windowed-core
 // call surfaces here too.  Host arrays (on_device false) are uploaded on D.s() into D.scratch[0] (160-byte points) and
 // D.scratch[1] (40-byte scalars) and the pointers redirected; a null array is skipped (zc_msm_fixed: the points are the table's).
@@ -1110,11 +1180,11 @@ int msm_stage(DevState& D, bool on_device, const u64** points, size_t npoints, c
     const size_t bytes[2] = {npoints * 160, nscalars * 40};
     for (int a = 0; a < 2; a++)
         if (arr[a])
-            if (int rc = ensure(&D.scratch[a], &D.scratch_bytes[a], bytes[a])) return rc;
+            if (int rc = D.scratch[a].grow(bytes[a])) return rc;
     for (int a = 0; a < 2; a++) {
         if (!arr[a]) continue;
-        HIP_TRY(hipMemcpyAsync(D.scratch[a], *arr[a], bytes[a], hipMemcpyHostToDevice, D.s()));
-        *arr[a] = (const u64*)D.scratch[a];
+        HIP_TRY(hipMemcpyAsync(D.scratch[a].as<void>(), *arr[a], bytes[a], hipMemcpyHostToDevice, D.s()));
+        *arr[a] = D.scratch[a].as<const u64>();
     }
     return ZC_OK;
 }
@@ -1139,9 +1209,9 @@ int msm_batch_on_device(DevState& D, const u64* dP, const u64* dK, size_t n, siz
     if (!bp.buckets) {
         // two buffers of the workspace: the batch n products, and the other side of the folds' ping-pong
         const size_t prod_bytes = (cnt * 160 + 255) & ~(size_t)255, half_bytes = (batch * ((n + 1) / 2) * 160 + 255) & ~(size_t)255;
-        if (int rc = ensure(&D.msm, &D.msm_bytes, prod_bytes + half_bytes)) return rc;
-        u64* cur = (u64*)D.msm;
-        u64* nxt = (u64*)((char*)D.msm + prod_bytes);
+        if (int rc = D.msm.grow(prod_bytes + half_bytes)) return rc;
+        u64* cur = D.msm.as<u64>();
+        u64* nxt = (u64*)(D.msm.as<char>() + prod_bytes);
         scalar_mul_on_device(D, dP, dK, cur, cnt);
         // every level halves every row: rows of n, ceil(n / 2), ... points, ping-pong between the two buffers
         for (size_t len = n; len > 1; len = (len + 1) / 2) {
@@ -1241,42 +1311,16 @@ int zc_ctx_create(const int* devices, int ndev, zc_ctx** out)
             ids.push_back(devices[i]);
         }
     }
-    zc_ctx* ctx = new zc_ctx();
+    std::unique_ptr<zc_ctx> ctx(new zc_ctx());                // a failing step below releases what the steps before it created
     const Tuning tune = tuning_from_env();                   // the only place the library reads its knobs
+    ctx->devs.reserve(ids.size());                           // the slots never move: pointers to them are taken everywhere
     for (int id : ids) {
-        DevState ds;
-        ds.device = id;
-        ds.tune = tune;
-        hipError_t e = hipSetDevice(id);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&ds.cus, hipDeviceAttributeMultiprocessorCount, id);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ds.stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ds.copy_in, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ds.copy_out, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ds.ev_order, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            int lo_p = 0, hi_p = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);         // lowest, highest (numerically smaller = higher)
-            e = hipStreamCreateWithPriority(&ds.aux, hipStreamNonBlocking, lo_p);
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ds.ev_fork, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ds.ev_join, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            int lo_p = 0, hi_p = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
-            e = hipStreamCreateWithPriority(&ds.grp, hipStreamNonBlocking, ZC_MSM_TAIL_PRIO ? hi_p : 0);
-        }
-        for (int g = 0; g < 3 && e == hipSuccess; g++) {
-            e = hipEventCreateWithFlags(&ds.ev_grp_go[g], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ds.ev_grp_done[g], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) {
-            delete ctx;
-            return fail(ZC_ERR_HIP, "stream creation", e);
-        }
-        ctx->devs.push_back(ds);
+        ctx->devs.emplace_back();
+        const hipError_t e = ctx->devs.back().open(id, tune);
+        if (e != hipSuccess) return fail(ZC_ERR_HIP, "stream creation", e);
     }
     (void)hipSetDevice(ids[0]);
-    *out = ctx;
+    *out = ctx.release();
     return ZC_OK;
 }
 
@@ -1287,43 +1331,11 @@ int zc_ctx_device(zc_ctx* ctx, int slot)
 }
 int zc_ctx_device_count(zc_ctx* ctx) { return ctx ? (int)ctx->devs.size() : fail(ZC_ERR_BAD_ARG, "null context"); }
 
+// Every slot drains its streams and releases what it holds (~DevState), then the fixed-base tables go.
 int zc_ctx_destroy(zc_ctx* ctx)
 {
     if (!ctx) return ZC_OK;
     if (ctx->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
-    for (auto& ds : ctx->devs) {
-        (void)hipSetDevice(ds.device);
-        (void)hipStreamSynchronize(ds.s());
-        if (ds.part) (void)hipFree(ds.part);
-        if (ds.ev_order) (void)hipEventDestroy(ds.ev_order);
-        if (ds.ev_fork) (void)hipEventDestroy(ds.ev_fork);
-        if (ds.ev_join) (void)hipEventDestroy(ds.ev_join);
-        if (ds.aux) (void)hipStreamDestroy(ds.aux);
-        if (ds.grp) (void)hipStreamSynchronize(ds.grp), (void)hipStreamDestroy(ds.grp);
-        for (int g = 0; g < 3; g++) {
-            if (ds.ev_grp_go[g]) (void)hipEventDestroy(ds.ev_grp_go[g]);
-            if (ds.ev_grp_done[g]) (void)hipEventDestroy(ds.ev_grp_done[g]);
-        }
-        for (int a = 0; a < MAX_ARGS; a++)
-            if (ds.scratch[a]) (void)hipFree(ds.scratch[a]);
-        for (int a = 0; a < 2; a++)
-            if (ds.tmp[a]) (void)hipFree(ds.tmp[a]);
-        if (ds.bal) (void)hipFree(ds.bal);
-        if (ds.msm) (void)hipFree(ds.msm);
-        if (ds.fast) (void)hipFree(ds.fast);
-        if (ds.ring) (void)hipFree(ds.ring);
-        if (ds.ring_err) (void)hipHostFree((void*)ds.ring_err);
-        if (ds.base_table) (void)hipFree(ds.base_table);
-        if (ds.odd_table) (void)hipFree(ds.odd_table);
-        for (hipEvent_t e : ds.ev) (void)hipEventDestroy(e);
-        if (ds.copy_in) (void)hipStreamDestroy(ds.copy_in);
-        if (ds.copy_out) (void)hipStreamDestroy(ds.copy_out);
-        if (ds.stream) (void)hipStreamDestroy(ds.stream);
-    }
-    for (auto& kv : ctx->bases) {
-        (void)hipSetDevice(ctx->devs[(size_t)kv.second.slot].device);
-        (void)hipFree(kv.second.recs);
-    }
     delete ctx;
     return ZC_OK;
 }
@@ -1605,16 +1617,29 @@ int zc_proj_scalar_mul(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64
 }
 
 // ---- fixed-base multiplication of the basepoint
+// A table the slot builds on first use and keeps: allocated once, filled by `builder` (one workgroup of `block` lanes) on D.s().
+// A builder whose launch is refused leaves no table behind.
+static int lazy_table(DevState& D, DevBuf& buf, size_t bytes, void (*builder)(zc::u32*), unsigned block, const zc::u32** table)
+{
+    if (!buf) {
+        if (int rc = buf.grow(bytes)) return rc;
+        hipLaunchKernelGGL(builder, dim3(1), dim3(block), 0, D.s(), buf.as<zc::u32>());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)buf.reset();
+            return fail(ZC_ERR_HIP, "device table build", e);
+        }
+    }
+    *table = buf.as<const zc::u32>();
+    return ZC_OK;
+}
 static int base_table(DevState& D, const zc::u32** table)
 {
-    if (!D.base_table) {
-        int rc = ensure(&D.base_table, &D.base_bytes, (size_t)zc::ZC_BASE_WINDOWS * zc::ZC_BASE_ENTRIES * 128);
-        if (rc) return rc;
-        hipLaunchKernelGGL(zc::k_base_table_build, dim3(1), dim3(zc::ZC_BASE_ENTRIES), 0, D.s(), (zc::u32*)D.base_table);
-        HIP_TRY(hipGetLastError());
-    }
-    *table = (const zc::u32*)D.base_table;
-    return ZC_OK;
+    return lazy_table(D, D.base_table, (size_t)zc::ZC_BASE_WINDOWS * zc::ZC_BASE_ENTRIES * 128, zc::k_base_table_build, zc::ZC_BASE_ENTRIES, table);
+}
+static int odd_table(DevState& D, const zc::u32** table)
+{
+    return lazy_table(D, D.odd_table, (size_t)zc::ZC_ODD_ENTRIES * 128, zc::k_odd_table_build, 128, table);
 }
 int zc_ed_mul_base(zc_ctx* ctx, const uint64_t* k, uint64_t* out, size_t n)
 {
@@ -1664,11 +1689,9 @@ int zc_ed_mul_base_wnaf(zc_ctx* ctx, const uint64_t* k, unsigned width, uint64_t
 {
     if (width < 2 || width > 7) return fail(ZC_ERR_BAD_ARG, "zc_ed_mul_base_wnaf: window width 2..7 (compute_window_NAF's digits are i8)");
     return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, u64* dout) -> int {
-        if (!D.odd_table) {
-            if (int rc = ensure(&D.odd_table, &D.odd_bytes, (size_t)zc::ZC_ODD_ENTRIES * 128)) return rc;
-            hipLaunchKernelGGL(zc::k_odd_table_build, dim3(1), dim3(128), 0, D.s(), (zc::u32*)D.odd_table);
-        }
-        hipLaunchKernelGGL(zc::k_ed_mul_base_wnaf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, (zc::u32)width, dout, (const zc::u32*)D.odd_table, cnt);
+        const zc::u32* t = nullptr;
+        if (int rc = odd_table(D, &t)) return rc;
+        hipLaunchKernelGGL(zc::k_ed_mul_base_wnaf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, (zc::u32)width, dout, t, cnt);
         return ZC_OK;
     }, ROWS(k, 5), ROWS(out, 20));
 }
@@ -1690,9 +1713,8 @@ static int gather_and_fold(zc_ctx* ctx, const std::vector<DevState*>& used, cons
         return ZC_OK;
     }
     HIP_TRY(hipSetDevice(d0->device));
-    int rc = ensure(&d0->part, &d0->part_bytes, (np + 1) * 160);
-    if (rc) return rc;
-    u64* part = (u64*)d0->part;
+    if (int rc = d0->part.grow((np + 1) * 160)) return rc;
+    u64* part = d0->part.as<u64>();
     for (size_t ui = 0; ui < np; ui++) {
         DevState* ds = used[ui];
         HIP_TRY(hipSetDevice(ds->device));
@@ -1715,7 +1737,7 @@ static int gather_and_fold(zc_ctx* ctx, const std::vector<DevState*>& used, cons
 static int msm_local(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, size_t n, DevState** owner, const u64** result)
 {
     DevState* ds = nullptr;
-    if (int rc = msm_inputs_owner(ctx, points, scalars, "", &ds)) return rc;
+    if (int rc = owner_of(ctx, {points, scalars}, "", &ds)) return rc;
     std::vector<DevState*> used;
     std::vector<const u64*> partial_ptr;
     if (ds) {
@@ -1816,12 +1838,9 @@ int zc_test_odd_table(zc_ctx* ctx, uint64_t* out_dev_points)
     std::lock_guard<std::mutex> lock(ctx->mu);
     DevState& D = ctx->devs[0];
     HIP_TRY(hipSetDevice(D.device));
-    if (!D.odd_table) {
-        int rc = ensure(&D.odd_table, &D.odd_bytes, (size_t)zc::ZC_ODD_ENTRIES * 128);
-        if (rc) return rc;
-        hipLaunchKernelGGL(zc::k_odd_table_build, dim3(1), dim3(128), 0, D.s(), (zc::u32*)D.odd_table);
-    }
-    hipLaunchKernelGGL(zc::k_test_odd_table_dump, dim3(1), dim3(128), 0, D.s(), (const zc::u32*)D.odd_table, (u64*)out_dev_points);
+    const zc::u32* t = nullptr;
+    if (int rc = odd_table(D, &t)) return rc;
+    hipLaunchKernelGGL(zc::k_test_odd_table_dump, dim3(1), dim3(128), 0, D.s(), t, (u64*)out_dev_points);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(D.s()));
     return ZC_OK;
@@ -1875,53 +1894,41 @@ int zc_msm_bases_create(zc_ctx* ctx, const uint64_t* points, size_t n, int windo
     int c = 0, W = 0;
     if (int rc = msm_fixed_check(n, window_bits, &c, &W, "zc_msm_bases_create")) return rc;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Residency rp;
-    int dp = -1;
-    residency_of(points, &rp, &dp);
-    int slot = 0;
-    if (rp == RES_DEVICE) {
-        DevState* ds = dev_state_of(ctx, dp);
-        if (!ds) return fail(ZC_ERR_MIXED_MEM, "zc_msm_bases_create: points on a device outside this context");
-        slot = (int)(ds - ctx->devs.data());
-    }
-    DevState& D = ctx->devs[(size_t)slot];
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {points}, "zc_msm_bases_create: ", &owner)) return rc;
+    DevState& D = owner ? *owner : ctx->devs[0];
     if (int rc = ring_check(D)) return rc;
     HIP_TRY(hipSetDevice(D.device));
     MsmBases t;
-    t.slot = slot;
+    t.slot = (int)(&D - ctx->devs.data());
     t.n = n;
     t.c = c;
     t.W = W;
-    t.bytes = n * (size_t)W * ZC_MSM_REC_STRIDE;
     // window 0 = the points (copied: 16-byte aligned, plain), window j = 2^c times window j - 1, each normalised into its part of
     // the table; the two n-point buffers live for this call only
-    void* pts[2] = {nullptr, nullptr};
-    auto cleanup = [&](int rc) {
-        (void)hipStreamSynchronize(D.s());
-        for (void* b : pts)
-            if (b) (void)hipFree(b);
-        if (rc && t.recs) (void)hipFree(t.recs);
-        return rc;
+    DevBuf pts[2];
+    auto enqueue = [&]() -> int {
+        if (int rc = t.recs.alloc(n * (size_t)W * ZC_MSM_REC_STRIDE, "zc_msm_bases_create: hipMalloc(table)")) return rc;
+        for (DevBuf& b : pts)
+            if (int rc = b.alloc(n * 160, "zc_msm_bases_create: hipMalloc(points)")) return rc;
+        hipError_t e = hipMemcpyAsync(pts[0].as<void>(), points, n * 160, owner ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, D.s());
+        if (e != hipSuccess) return fail(ZC_ERR_HIP, "zc_msm_bases_create: copy of the points", e);
+        const zc::u32 rec_words = ZC_MSM_REC_STRIDE / 4;
+        for (int j = 0; j < W; j++) {
+            if (j) hipLaunchKernelGGL(zc::k_msm_fixed_double, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), pts[(j - 1) & 1].as<const u64>(), pts[j & 1].as<u64>(), n, c);
+            msm_prepare_affine(D.s(), pts[j & 1].as<const u64>(), t.recs.as<zc::u32>() + (size_t)j * n * rec_words, n, D.tune, rec_words);
+        }
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(ZC_ERR_HIP, "zc_msm_bases_create: table build", e);
+        return ZC_OK;
     };
-    hipError_t e = hipMalloc(&t.recs, t.bytes);
-    if (e != hipSuccess) return t.recs = nullptr, cleanup(fail(ZC_ERR_NOMEM, "zc_msm_bases_create: hipMalloc(table)", e));
-    for (int b = 0; b < 2; b++) {
-        e = hipMalloc(&pts[b], n * 160);
-        if (e != hipSuccess) return pts[b] = nullptr, cleanup(fail(ZC_ERR_NOMEM, "zc_msm_bases_create: hipMalloc(points)", e));
-    }
-    e = hipMemcpyAsync(pts[0], points, n * 160, rp == RES_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, D.s());
-    if (e != hipSuccess) return cleanup(fail(ZC_ERR_HIP, "zc_msm_bases_create: copy of the points", e));
-    const zc::u32 rec_words = ZC_MSM_REC_STRIDE / 4;
-    for (int j = 0; j < W; j++) {
-        if (j) hipLaunchKernelGGL(zc::k_msm_fixed_double, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)pts[(j - 1) & 1], (u64*)pts[j & 1], n, c);
-        msm_prepare_affine(D.s(), (const u64*)pts[j & 1], (zc::u32*)t.recs + (size_t)j * n * rec_words, n, D.tune, rec_words);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(D.s());
-    if (e != hipSuccess) return cleanup(fail(ZC_ERR_HIP, "zc_msm_bases_create: table build", e));
-    cleanup(ZC_OK);
+    // whatever was enqueued is through before the buffers go: the two point arrays with this call, the table too when a step failed
+    int rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(D.s());
+    if (!rc && e != hipSuccess) rc = fail(ZC_ERR_HIP, "zc_msm_bases_create: table build", e);
+    if (rc) return rc;
     const uint64_t id = g_next_bases_id.fetch_add(1);
-    ctx->bases[id] = t;
+    ctx->bases.emplace(id, std::move(t));
     *id_out = id;
     return ZC_OK;
 }
@@ -1935,9 +1942,9 @@ int zc_msm_bases_destroy(zc_ctx* ctx, uint64_t id)
     DevState& D = ctx->devs[(size_t)it->second.slot];
     HIP_TRY(hipSetDevice(D.device));
     HIP_TRY(hipStreamSynchronize(D.s()));
-    void* recs = it->second.recs;
+    const hipError_t freed = it->second.recs.reset();
     ctx->bases.erase(it);
-    HIP_TRY(hipFree(recs));
+    HIP_TRY(freed);
     return ZC_OK;
 }
 
@@ -1958,12 +1965,11 @@ int zc_msm_fixed(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, size_t batch
     if (limit == zc::MSM_LIMIT_PAIRS) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x n x W does not fit 32-bit pair indices");
     if (limit == zc::MSM_LIMIT_KEYS) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x 2^(c-1) buckets do not fit 32-bit bucket keys");
     DevState& D = ctx->devs[(size_t)t.slot];
-    Residency rk;
-    int dk = -1;
-    residency_of(scalars, &rk, &dk);
-    if (rk == RES_DEVICE && dk != D.device) return fail(ZC_ERR_MIXED_MEM, "zc_msm_fixed: scalars on another device than the table");
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {scalars}, "zc_msm_fixed: ", &owner)) return rc;
+    if (owner && owner->device != D.device) return fail(ZC_ERR_MIXED_MEM, "zc_msm_fixed: scalars on another device than the table");
     const u64* dK = scalars;
-    if (int rc = msm_stage(D, rk == RES_DEVICE, nullptr, 0, &dK, batch * n)) return rc;
+    if (int rc = msm_stage(D, owner != nullptr, nullptr, 0, &dK, batch * n)) return rc;
     const MsmBucketPlan fp = msm_fixed_plan(n, c, batch, D.tune.msm);
     MsmWorkspace ws;
     if (int rc = msm_workspace(D, fp, 0, 0, &ws)) return rc;
@@ -1971,7 +1977,7 @@ int zc_msm_fixed(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, size_t batch
     HIP_TRY(hipMemsetAsync(ws.present, 0, fp.nb, D.s()));
     if (int rc = msm_sort(D, D.s(), fp.sort, 0, (int)batch, ws.digits, ws.pairs_a, ws.pairs_b, ws.sort_table, fp.sort.table_words, ws.sort_sums)) return rc;
     u64* sums = nullptr;
-    if (int rc = msm_reduce_windows(D, msm_reduce_bufs(fp, ws, (const zc::u32*)t.recs), msm_reduce_flat(fp, ws), &sums)) return rc;
+    if (int rc = msm_reduce_windows(D, msm_reduce_bufs(fp, ws, t.recs.as<const zc::u32>()), msm_reduce_flat(fp, ws), &sums)) return rc;
     // the folds leave the batch's sums as canonical extended points, one per vector in order
     HIP_TRY(hipMemcpyAsync(out_points, sums, batch * 160, hipMemcpyDeviceToHost, D.s()));
     HIP_TRY(hipStreamSynchronize(D.s()));
@@ -2011,7 +2017,7 @@ int zc_msm_batch(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, s
     if (int rc = msm_batch_check(n, batch, ctx->devs[0].tune, "zc_msm_batch")) return rc;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DevState* owner = nullptr;
-    if (int rc = msm_inputs_owner(ctx, points, scalars, "zc_msm_batch: ", &owner)) return rc;
+    if (int rc = owner_of(ctx, {points, scalars}, "zc_msm_batch: ", &owner)) return rc;
     DevState& D = owner ? *owner : ctx->devs[0];
     const u64* res = nullptr;
     if (batch == 1) {
@@ -2058,12 +2064,9 @@ int zc_msm_partial(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars,
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     REQUIRE(out_dev_point);
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Residency ro;
-    int dvo = -1;
-    residency_of(out_dev_point, &ro, &dvo);
-    if (ro != RES_DEVICE) return fail(ZC_ERR_MIXED_MEM, "zc_msm_partial: out_dev_point must be device memory");
-    DevState* od = dev_state_of(ctx, dvo);
-    if (!od) return fail(ZC_ERR_MIXED_MEM, "device buffers do not belong to a device of this context");
+    DevState* od = nullptr;
+    if (int rc = owner_of(ctx, {out_dev_point}, "", &od)) return rc;
+    if (!od) return fail(ZC_ERR_MIXED_MEM, "zc_msm_partial: out_dev_point must be device memory");
     if (n == 0) {
         HIP_TRY(hipSetDevice(od->device));
         HIP_TRY(hipMemcpyAsync(out_dev_point, IDENT_POINT, 160, hipMemcpyHostToDevice, od->s()));
@@ -2088,24 +2091,19 @@ int zc_ed_fold_ordered(zc_ctx* ctx, const uint64_t* parts, size_t count, uint64_
     REQUIRE(parts); REQUIRE(out);
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     if (count == 0) return fail(ZC_ERR_BAD_ARG, "zc_ed_fold_ordered: empty list");
-    Residency rp, ro;
-    int dp = -1, dvo = -1;
-    residency_of(parts, &rp, &dp);
-    residency_of(out, &ro, &dvo);
-    if (rp != ro || (rp == RES_DEVICE && dp != dvo)) return fail(ZC_ERR_MIXED_MEM, "host and device buffers mixed in one call");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    DevState* ds = rp == RES_DEVICE ? dev_state_of(ctx, dp) : &ctx->devs[0];
-    if (!ds) return fail(ZC_ERR_MIXED_MEM, "device buffers do not belong to a device of this context");
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {parts, out}, "", &owner)) return rc;
+    DevState* ds = owner ? owner : &ctx->devs[0];
     if (int rc = ring_check(*ds)) return rc;
     HIP_TRY(hipSetDevice(ds->device));
-    if (rp == RES_DEVICE) {
+    if (owner) {
         hipLaunchKernelGGL(zc::k_ed_fold_ordered, dim3(1), dim3(64), 0, ds->s(), (const u64*)parts, count, (const u64*)nullptr, (u64*)out);
         HIP_TRY(hipGetLastError());
         return ZC_OK;
     }
-    int rc = ensure(&ds->part, &ds->part_bytes, (count + 1) * 160);
-    if (rc) return rc;
-    u64* part = (u64*)ds->part;
+    if (int rc = ds->part.grow((count + 1) * 160)) return rc;
+    u64* part = ds->part.as<u64>();
     HIP_TRY(hipMemcpyAsync(part, parts, count * 160, hipMemcpyHostToDevice, ds->s()));
     hipLaunchKernelGGL(zc::k_ed_fold_ordered, dim3(1), dim3(64), 0, ds->s(), (const u64*)part, count, (const u64*)nullptr, part + 20 * count);
     HIP_TRY(hipGetLastError());
@@ -2186,9 +2184,8 @@ int zc_msm_sharded(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars,
     const size_t world = (size_t)ctx->world;
     HIP_TRY(hipSetDevice(d0->device));
     const size_t front = ctx->devs.size() + 1;               // gather_and_fold's region (multi-slot host inputs)
-    int rc = ensure(&d0->part, &d0->part_bytes, (front + world + 2) * 160);
-    if (rc) return rc;                                       // nothing to send from: the one failure that cannot join
-    u64* gathered = (u64*)d0->part + 20 * front;
+    if (int rc = d0->part.grow((front + world + 2) * 160)) return rc;   // nothing to send from: the one failure that cannot join
+    u64* gathered = d0->part.as<u64>() + 20 * front;
     u64* mine = gathered + 20 * world;                       // mine, then the folded result
     int local_rc = ZC_OK;
     std::string local_err;

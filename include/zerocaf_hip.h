@@ -27,6 +27,13 @@
  * in the caller's buffer.  Device buffers are used in place: the kernels are
  * enqueued on the context's stream and the call returns immediately -- order
  * later work on the same stream or call zc_ctx_synchronize().
+ * ALIGNMENT of DEVICE arrays: every array, the byte arrays (32- and 64-byte encodings) included, must start on an 8-byte
+ * boundary -- what a `uint64_t *` has anyway; the kernels read and write encodings as 64-bit words.  Nothing more is needed:
+ * limb arrays on a 16-byte boundary take faster (LDS-staged) forms of some kernels, arrays 8 bytes off one take the per-lane
+ * forms, with identical results.  Two exceptions take device byte arrays at ANY address: the inputs of zc_sc_from_bytes_wide
+ * and zc_sc_from_bytes_mod_order.  Accept masks and flag outputs are bytes and need no alignment.  HOST arrays may sit at
+ * any address (they are copied into the library's own aligned staging buffers).  The library writes rows 0 .. n-1 of its
+ * outputs and nothing else: no byte before or after them, and no byte of an input.
  *
  * Return value: 0 on success, negative zc_status on error.  Where the reference
  * panics or returns None for an individual element (inverse of 0, undecodable

@@ -1,0 +1,188 @@
+// zc_ris_batch.hip.h -- batched Ristretto encoders whose rows share work (zc_ris_double_and_compress).
+//
+// out = RistrettoPoint(2 P).compress(): the reference's Double (edwards.rs:579-592) followed by compress
+// (ristretto.rs:398-425), without the square root.  compress pays one (p-5)/8 power per row (about 250 squarings, 265
+// multiplications in all) that nothing can share.  The encoding of a DOUBLED point needs only the inverse of a product, and
+// Montgomery's trick shares one inversion among the rows of a lane.  With d = EDWARDS_D, for a row (X : Y : Z : T):
+//     e = 2 X Y    f = Z^2 + d T^2    g = Y^2 + X^2    h = Z^2 - d T^2         (2P = (e f : g h : f h : e g), a = -1)
+//     w = (e g) (f h)                   the one value to invert
+//     Zinv = (e g) / w = 1 / (f h)      Tinv = (f h) / w = 1 / (e g)
+//     magic = INV_SQRT_A_MINUS_D
+//     if !is_positive(e g Zinv): (e, g, h, magic) = (g, -e, f SQRT_MINUS_ONE, SQRT_MINUS_ONE)
+//     if !is_positive(h e Zinv): g = -g
+//     s = (h - g) magic g Tinv;  out = to_bytes(|s|)
+// Every quantity a decision reads has degree 0 in the coordinates, so any representative of the point gives the same bytes.
+// The two negations only change the sign of g, and |s| is taken last: with g' the unsigned choice (e or g) and tau the product
+// of the two signs, |s| = |(h - tau g') g' magic Tinv| -- a subtraction or an addition, no negated value is ever formed.
+//
+// Multiplications per row (squarings counted as multiplications): the terms 6 (X Y, X^2, Y^2, Z^2, T^2, d T^2), e g, f h and
+// w 3: 9 in either pass (the limbs are used as they come: no conversion into the Montgomery domain).  Forward pass 9 + 1
+// (running product) = 10; backward pass 9 + 2 (peel the inverse, step it) + 2 (Zinv, Tinv) + 1 (first sign) + 1 (f i) + 2
+// (second sign) + 3 (s) = 20; three leaves of the domain for the sign tests and two for the zero test, half a
+// multiplication each.  About 32 per row plus 1 / c of a division-step inversion (about 45), against about 265 for
+// ris_compress after a doubling's 9.  (A wave that holds a coordinate of 1.5 * 2^252 or more pays 8 more.)
+//
+// Zero by value: w = 0 mod p exactly for the points of E[8] (e g = 0: X Y = 0 or X^2 + Y^2 = 0) and for Z = 0, T = 0 garbage;
+// the reference's composition returns 32 zero bytes for E[8].  Such a row takes the neutral value in the shared product, gets
+// 32 zero bytes, and changes nothing in its lane (the rule of fe_invert_chunk and ed_to_affine_chunk).  Rows off the curve get
+// bytes that depend on their own words only; every launch form decides by canonical values, so the forms agree byte for byte.
+#pragma once
+#include "zc_curve.hip.h"
+
+namespace zc {
+
+struct ris_dc_terms {
+    fe e, f, g, h;       // e, f, g lazy (limbs < 2^30), h normalized and below 8N
+    fe eg, fh, w;        // R-class
+    bool zero;           // w = 0 mod p
+};
+
+template <bool ILP>
+ZC_DI fe ris_dc_mul(const fe& x, const fe& y) { return ILP ? mont_mul_ilp<FP>(x, y) : mont_mul<FP>(x, y); }
+template <bool ILP>
+ZC_DI fe ris_dc_sqr(const fe& x) { return ILP ? mont_sqr_ilp<FP>(x) : mont_sqr<FP>(x); }
+
+// e, f, g, h and their products for the record at `row` (twenty words, any: a word's bits from 2^52 up are not read)
+template <bool ILP>
+ZC_DI ris_dc_terms ris_dc_load(const u64* __restrict__ row)
+{
+    // The plain limbs serve as Montgomery residues (of X / R ...: one common factor, and the encoding does not depend on the
+    // representative).  The bounds below want operands under 1.5 N: a top limb below 1.5 * 2^44, as every canonical value
+    // has.  Anything larger is reduced first (x (R mod N) / R = x, below 1.5 N) -- by the whole wave, so that honest batches
+    // never diverge; the residue is the same either way, and nothing below depends on more than the residue.
+    fe c[4];
+    bool big = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        u64 l[5];
+        load5(l, row + 5 * k);
+        c[k] = fe_from_limbs52(l);
+        big |= ((l[4] & M52) >> 43) >= 3;
+    }
+    if (wave_any(big)) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) c[k] = ris_dc_mul<ILP>(c[k], fe_one_m<FP>());
+    }
+    ris_dc_terms t;
+    const fe xy = ris_dc_mul<ILP>(c[0], c[1]);
+    const fe zz = ris_dc_sqr<ILP>(c[2]);
+    const fe dtt = ris_dc_mul<ILP>(fe_const<FP>(ModP::D_M), ris_dc_sqr<ILP>(c[3]));
+    t.e = fe_add(xy, xy);
+    t.g = fe_add(ris_dc_sqr<ILP>(c[1]), ris_dc_sqr<ILP>(c[0]));
+    t.f = fe_add(zz, dtt);
+    t.h = fp_sub(zz, dtt);
+    t.eg = ris_dc_mul<ILP>(t.e, t.g);
+    t.fh = ris_dc_mul<ILP>(t.f, t.h);
+    t.w = ris_dc_mul<ILP>(t.eg, t.fh);
+    t.zero = fp_is_zero(t.w);
+    return t;
+}
+
+// The row's 32 bytes as four words from its terms and winv = 1 / w (Montgomery form, R-class); zeros for a row with w = 0.
+template <bool ILP>
+ZC_DI void ris_dc_finish(u64 (&out)[4], const ris_dc_terms& t, const fe& winv)
+{
+    const fe zinv = ris_dc_mul<ILP>(t.eg, winv);
+    const fe tinv = ris_dc_mul<ILP>(t.fh, winv);
+    const bool rotate = !fp_is_positive(ris_dc_mul<ILP>(t.eg, zinv));
+    fe e = t.e, g = t.g;
+    fe_carry(e);                                                             // sums of two products of operands below 1.5 N: below 2.02 N,
+    fe_carry(g);                                                             // R-class once the limbs are normalized
+    const fe e2 = fe_select(rotate, g, e);
+    const fe g2 = fe_select(rotate, e, g);                                   // unsigned: the sign is (rotate ? -1 : +1)
+    const fe h2 = fe_select(rotate, ris_dc_mul<ILP>(t.f, fe_const<FP>(ModP::SQRT_M1_M)), t.h);
+    const fe magic = fe_select(rotate, fe_const<FP>(ModP::SQRT_M1_M), fe_const<FP>(ModP::INV_SQRT_A_MINUS_D_M));
+    const bool negate = !fp_is_positive(ris_dc_mul<ILP>(h2, ris_dc_mul<ILP>(e2, zinv)));
+    const fe diff = fe_select(rotate != negate, fe_add(h2, g2), fp_sub(h2, g2));       // h - tau g'
+    const fe s = ris_dc_mul<ILP>(ris_dc_mul<ILP>(ris_dc_mul<ILP>(diff, magic), g2), tinv);
+    const fe sc = fp_canon(s);
+    fe_to_words256(out, fe_select(fe_is_positive_canon<FP>(sc), sc, fe_n_minus_canon<FP>(sc)));
+    if (t.zero) out[0] = out[1] = out[2] = out[3] = 0;
+}
+
+// One row on its own: one inversion (k_ris_double_compress, small batches).
+ZC_DI void ris_double_compress_row(u64 (&out)[4], const u64* __restrict__ row)
+{
+    const ris_dc_terms t = ris_dc_load<false>(row);
+    ris_dc_finish<false>(out, t, fp_invert(t.w));                            // 0 -> 0, and the row's bytes are zeroed
+}
+
+// One lane's share of the batch: Montgomery's trick over w of the up to `c` rows lo, lo + stride, ... (as ed_to_affine_chunk:
+// stride = number of lanes, so that the lanes of a wave touch neighbouring records in both passes).  The forward pass forms
+// w_j and parks the running product of the rows before j; one inversion; the backward pass forms the row's terms again from its
+// record, peels 1 / w_j off the running inverse and finishes the row.
+//
+// Where the prefix products wait: the call may write nothing but its 32-byte output rows, and the nine-word register form
+// the other chunked kernels park does not fit one.  So the prefix is made canonical (two conditional subtractions: it is
+// below 3N) and parked as a 256-bit integer in the row's OWN output bytes, which the backward pass replaces with the encoding.
+// The load in the backward pass must be issued by the lane that stored, with the same address: a lane's own global stores
+// and loads to one address stay in program order, nothing orders them against another lane's without a fence.  Both passes
+// derive the address from (lo, stride, j) alone, and `out32` must not overlap `p` (the record is read again after the store).
+template <bool ILP = false>
+ZC_DI void ris_double_compress_chunk(const u64* p, uint8_t* out32, size_t n, size_t lo, size_t stride, int c)
+{
+    const size_t avail = (n - lo + stride - 1) / stride;
+    const int cnt = (int)(avail < (size_t)c ? avail : (size_t)c);
+    const fe neutral = fe_one_m<FP>();
+    fe acc = neutral;
+    for (int j = 0; j < cnt; j++) {
+        const size_t i = lo + (size_t)j * stride;
+        const ris_dc_terms t = ris_dc_load<ILP>(p + 20 * i);
+        u64 park[4];
+        fe_to_words256(park, fe_cond_sub_n<FP>(fe_cond_sub_n<FP>(acc)));     // the product of the rows before j, times R
+        u64* slot = reinterpret_cast<u64*>(out32 + 32 * i);                  // 32-byte records, 8-byte aligned
+#pragma unroll
+        for (int k = 0; k < 4; k++) slot[k] = park[k];
+        acc = ris_dc_mul<ILP>(acc, fe_select(t.zero, neutral, t.w));
+    }
+    // plain inverse of the register value, times R^3: inv pre / R = R / w_j, the Montgomery form of 1 / w_j, from here on
+    fe inv = ris_dc_mul<ILP>(fp_inverse_of_register(acc), fe_const<FP>(ModP::R3));
+    for (int j = cnt - 1; j >= 0; j--) {
+        const size_t i = lo + (size_t)j * stride;
+        const ris_dc_terms t = ris_dc_load<ILP>(p + 20 * i);
+        u64* slot = reinterpret_cast<u64*>(out32 + 32 * i);
+        u64 park[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) park[k] = slot[k];                       // this lane's own store of the forward pass
+        const fe winv = ris_dc_mul<ILP>(inv, fe_from_words256(park));
+        inv = ris_dc_mul<ILP>(inv, fe_select(t.zero, neutral, t.w));
+        ris_dc_finish<ILP>(park, t, winv);
+#pragma unroll
+        for (int k = 0; k < 4; k++) slot[k] = park[k];
+    }
+}
+
+}  // namespace zc
+
+// the kernels: hipcc only (the host emulation of the test tier builds the device functions above with a C++ compiler)
+#if defined(__HIPCC__)
+#include "zc_kernels.hip.h"
+
+namespace zc {
+
+// one row per lane, one inversion each: batches too small to share
+ZC_KERNEL void k_ris_double_compress(const u64* p, uint8_t* out32, size_t n)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    u64 w[4];
+    ris_double_compress_row(w, p + 20 * i);
+    u64* o = reinterpret_cast<u64*>(out32 + 32 * i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o[k] = w[k];
+}
+// `c` rows per lane share one inversion (ris_double_compress_chunk)
+ZC_KERNEL void k_ris_double_compress_chunked(const u64* p, uint8_t* out32, size_t n, int c)
+{
+    const size_t lanes = (n + (size_t)c - 1) / (size_t)c, g = gid();
+    if (g < lanes) ris_double_compress_chunk<false>(p, out32, n, g, lanes, c);
+}
+// the same for launches of at most one wave per SIMD, on the independent-chain multiplier
+ZC_KERNEL void k_ris_double_compress_chunked_lone(const u64* p, uint8_t* out32, size_t n, int c)
+{
+    const size_t lanes = (n + (size_t)c - 1) / (size_t)c, g = gid();
+    if (g < lanes) ris_double_compress_chunk<true>(p, out32, n, g, lanes, c);
+}
+
+}  // namespace zc
+#endif

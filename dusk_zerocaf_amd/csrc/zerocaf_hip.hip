@@ -24,8 +24,10 @@
 #include <rccl/rccl.h>      // types only: librccl is opened with dlopen when a communicator is requested
 
 #include "../../include/zerocaf_hip.h"
+#include "../../include/zerocaf_hip_ext.h"
 #include "zc_kernels.hip.h"
 #include "zc_msm.hip.h"
+#include "zc_ris_batch.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -1581,6 +1583,14 @@ int zc_ris_decompress(zc_ctx* ctx, const uint8_t* in32, uint64_t* out, uint8_t* 
     return batched(ctx, n, false, plain(zc::k_ris_decompress), ROWS(in32, 32), ROWS(out, 20), OPT_ROWS(ok, 1));
 }
 int zc_ris_eq(zc_ctx* ctx, const uint64_t* p, const uint64_t* q, uint8_t* eq, size_t n) { return batched(ctx, n, false, plain(zc::k_ris_eq), ROWS(p, 20), ROWS(q, 20), ROWS(eq, 1)); }
+// zerocaf_hip_ext.h: the encodings of 2 P, one shared inversion per lane instead of a square root per row (zc_ris_batch.hip.h)
+int zc_ris_double_and_compress(zc_ctx* ctx, const uint64_t* p, uint8_t* out32, size_t n)
+{
+    return batched(ctx, n, false, [](DevState& D, size_t cnt, const u64* dp, uint8_t* dout) {
+        // (a 160-byte row cannot be encoded in place; the prefix products wait in the output rows themselves)
+        return launch_shared_inversions(D, cnt, false, zc::k_ris_double_compress, zc::k_ris_double_compress_chunked, zc::k_ris_double_compress_chunked_lone, dp, dout);
+    }, ROWS(p, 20), ROWS(out32, 32));
+}
 int zc_ris_roundtrip_mul(zc_ctx* ctx, const uint8_t* in32, const uint64_t* k, uint8_t* out32, uint8_t* ok, size_t n)
 {
     // The boundary is encodings in / encodings out, which depend only on the group element, so

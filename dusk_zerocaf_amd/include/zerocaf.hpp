@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/zerocaf_hip.h"
+#include "../../include/zerocaf_hip_ext.h"
 
 namespace zerocaf {
 
@@ -640,6 +641,18 @@ inline void msm_partial(const uint64_t* points, const uint64_t* scalars, size_t 
     Backend::check(zc_msm_partial(Backend::ctx(), points, scalars, n, out_dev), "zc_msm_partial");
 }
 // k * BASEPOINT from the fixed-base table: equal to `BASEPOINT * k` under == (not limb-identical)
+// the encodings of 2 * P_i without a square root: the rows share inversions (zerocaf_hip_ext.h).  compress(k * P) for a point of
+// order L is this call on (k * 2^-1 mod L) * P; a point of E[8] gives 32 zero bytes, as the reference's composition does
+inline std::vector<CompressedRistretto> double_and_compress_batch(const std::vector<RistrettoPoint>& ps)
+{
+    std::vector<uint64_t> p(ps.size() * 20);
+    std::vector<uint8_t> o(ps.size() * 32);
+    for (size_t i = 0; i < ps.size(); i++) ps[i].p.flat(&p[20 * i]);
+    if (!ps.empty()) Backend::check(zc_ris_double_and_compress(Backend::ctx(), p.data(), o.data(), ps.size()), "zc_ris_double_and_compress");
+    std::vector<CompressedRistretto> out(ps.size());
+    for (size_t i = 0; i < ps.size(); i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
+    return out;
+}
 inline std::vector<EdwardsPoint> mul_base_batch(const std::vector<Scalar>& ks)
 {
     std::vector<uint64_t> k(ks.size() * 5), o(ks.size() * 20);

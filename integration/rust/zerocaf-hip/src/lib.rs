@@ -13,6 +13,7 @@
 //! compiled there.  The ABI underneath is exercised end to end through ctypes and C++.
 #![allow(non_snake_case)]
 
+pub mod ext;
 pub mod ffi;
 
 use std::ffi::CStr;

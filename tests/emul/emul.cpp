@@ -276,3 +276,66 @@ extern "C" void emul_scalar_effective(const u64* k, u64* out, int* nbits, size_t
         for (int j = 0; j < 5; j++) out[5 * i + j] = l[j];
     }
 }
+// ---- operations whose kernels spell their lane out inline (zc_kernels.hip.h: k_fe_mod_sqrt, k_fe_pow, k_fe_half, k_sc_half,
+// k_sc_pow, k_sc_invert): the same per-lane functions in the same order; is_positive through fp_is_positive, the rule every
+// codec applies (k_fe_is_positive itself compares the five words)
+template <class F>
+static void half_rows(const u64* a, u64* out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) {
+        u64 l[5], h[5];
+        ld5(l, a + 5 * i);
+        fe_to_limbs52(h, fe_n_minus_canon<F>(fe_const<F>(F::HALF)));                  // (N + 1) / 2 = N - (N - 1) / 2
+        store_plain<F>(out + 5 * i, mont_mul<F>(mont_to<F>(fe_from_limbs52(l)), fe_from_limbs52(h)));
+    }
+}
+extern "C" {
+void emul_fe_mod_sqrt(const u64* a, int sign, u64* out, uint8_t* ok, size_t n)
+{
+    for (size_t i = 0; i < n; i++) {
+        fe x;
+        const bool have = fp_mod_sqrt(x, fe_load_mont<FP>(a + 5 * i), sign != 0);
+        fe_store_canon<FP>(out + 5 * i, fe_select(have, x, fe_zero()));
+        ok[i] = have ? 1 : 0;
+    }
+}
+void emul_fe_pow(const u64* a, const u64* e, u64* out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) {
+        u64 l[5];
+        ld5(l, e + 5 * i);
+        fe_store_canon<FP>(out + 5 * i, fp_pow_var(fe_load_mont<FP>(a + 5 * i), fe_from_limbs52(l)));
+    }
+}
+void emul_fe_is_positive(const u64* a, uint8_t* out, size_t n)
+{ for (size_t i = 0; i < n; i++) out[i] = fp_is_positive(fe_load_mont<FP>(a + 5 * i)) ? 1 : 0; }
+void emul_fe_half(const u64* a, u64* out, size_t n) { half_rows<ModP>(a, out, n); }
+void emul_sc_half(const u64* a, u64* out, size_t n) { half_rows<ModL>(a, out, n); }
+void emul_sc_pow(const u64* a, const u64* e, u64* out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) {
+        u64 l[5];
+        ld5(l, e + 5 * i);
+        const fe ee = fe_from_limbs52(l);
+        const fe am = fe_load_mont<ModL>(a + 5 * i);
+        fe acc = fe_one_m<ModL>();
+        for (int b = 260; b >= 0; b--) {
+            acc = mont_sqr<ModL>(acc);
+            const bool bit = ((ee.v[b / 29] >> (b % 29)) & 1) != 0;
+            acc = fe_select(bit, mont_mul<ModL>(acc, am), acc);
+        }
+        fe_store_canon<ModL>(out + 5 * i, acc);
+    }
+}
+void emul_sc_invert_row(const u64* a, u64* out, uint8_t* ok, size_t n)
+{
+    for (size_t i = 0; i < n; i++) {
+        u64 l[5], r[5];
+        ld5(l, a + 5 * i);
+        bool nz;
+        sc_invert_limbs52(r, &nz, l);
+        for (int j = 0; j < 5; j++) out[5 * i + j] = r[j];
+        ok[i] = nz ? 1 : 0;
+    }
+}
+}

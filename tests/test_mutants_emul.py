@@ -1,0 +1,177 @@
+"""CPU tier: every planted defect of tests/mutants.py must be caught by the kill-vector family it names.
+
+Per entry the headers (dusk_zerocaf_amd/csrc/*.h) and the emulation sources (tests/emul/*.cpp) are copied into a temporary
+directory, the one replacement is applied to the copy, the one emulation library the entry's family needs is built from it
+with g++ (as the other emulation fixtures build theirs, no sanitizer), loaded with ctypes and the family run in-process: at
+least one comparison must fail.  The unmutated copy must pass every family, every `old` text must occur exactly once in its
+header, and the canary (fe_carry stopping at limb 7) must be killed.  Nothing is written inside the repository tree; the
+builds run on a thread pool of at most 16."""
+import concurrent.futures
+import ctypes as C
+import glob
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from tests import kill_vectors as KV
+from tests import mutants as M
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
+EMUL_DIR = os.path.join(HERE, "emul")
+ROCM_INC = "/opt/rocm/include"
+HEADERS = {M.ARITH: "zc_arith.hip.h", M.CURVE: "zc_curve.hip.h"}
+BY_NAME = {m["name"]: m for m in M.MUTANTS}
+
+
+def kind(m):
+    if "equivalent" in m:
+        return "equivalent"
+    if "rounds" in m and 30 * m["rounds"] >= M.S_MAX[m["family"][-1]]:          # longest_inversions_p / _l
+        return "not reached"
+    return "killed"
+
+
+def families_of(m):
+    return m["survives"] if "equivalent" in m else (m["family"],)
+
+
+def make_copy(where, m=None):
+    """The layout the emulation sources include through, with the entry's replacement applied to the copied header."""
+    csrc = os.path.join(where, "dusk_zerocaf_amd", "csrc")
+    emul = os.path.join(where, "tests", "emul")
+    os.makedirs(csrc)
+    os.makedirs(emul)
+    for f in glob.glob(os.path.join(CSRC, "*.h")):
+        shutil.copy(f, csrc)
+    for f in glob.glob(os.path.join(EMUL_DIR, "*.cpp")):
+        shutil.copy(f, emul)
+    if m is not None:
+        path = os.path.join(csrc, HEADERS[m["header"]])
+        with open(path) as f:
+            text = f.read()
+        assert text.count(m["old"]) == 1, m["name"]
+        with open(path, "w") as f:
+            f.write(text.replace(m["old"], m["new"]))
+    return where
+
+
+def build(where, lib):
+    so = os.path.join(where, "lib_%s.so" % lib)
+    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-fno-gnu-unique", "-Wl,-Bsymbolic",
+                           "-I" + ROCM_INC, "-o", so, os.path.join(where, "tests", "emul", KV.LIBS[lib])])
+    return so
+
+
+@pytest.fixture(scope="module")
+def built(tmp_path_factory):
+    """{entry name or None (the unmutated copy): {library: path}}, everything built up front on the pool."""
+    if not os.path.isdir(ROCM_INC):
+        pytest.skip("ROCm headers not present")
+    jobs = [(None, lib) for lib in KV.LIBS]
+    for m in M.MUTANTS:
+        jobs += [(m["name"], lib) for lib in sorted({KV.FAMILIES[f].lib for f in families_of(m)})]
+    dirs = {name: make_copy(str(tmp_path_factory.mktemp(name or "unmutated")), BY_NAME.get(name)) for name in {j[0] for j in jobs}}
+    out = {name: {} for name in dirs}
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        for (name, lib), so in zip(jobs, pool.map(lambda j: build(dirs[j[0]], j[1]), jobs)):
+            out[name][lib] = so
+    assert not any(p.startswith(ROOT + os.sep) for libs in out.values() for p in libs.values())
+    return out
+
+
+def failures(built, name, family):
+    lib = C.CDLL(built[name][KV.FAMILIES[family].lib])
+    return KV.run(family, KV.EmulBackend(lib))
+
+
+def test_catalogue_is_sound():
+    names = [m["name"] for m in M.MUTANTS]
+    assert len(names) == len(set(names)) and len(names) >= 40
+    headers = {k: open(os.path.join(CSRC, v)).read() for k, v in HEADERS.items()}
+    for m in M.MUTANTS:
+        assert headers[m["header"]].count(m["old"]) == 1, "%s: `old` occurs %d times" % (m["name"], headers[m["header"]].count(m["old"]))
+        assert m["old"] != m["new"] and all(f in KV.FAMILIES for f in families_of(m)), m["name"]
+        assert ("equivalent" in m) != ("family" in m) and ("equivalent" not in m or len(m["equivalent"]) > 80), m["name"]
+    kinds = [kind(m) for m in M.MUTANTS]
+    assert kinds.count("equivalent") <= 0.15 * len(kinds), kinds.count("equivalent")
+    # every family is the named killer of at least one entry: take a family away and that entry fails
+    assert {m["family"] for m, k in zip(M.MUTANTS, kinds) if k == "killed"} == set(KV.FAMILIES)
+    assert sum(1 for m in M.MUTANTS if m.get("canary")) == 1
+    # the rounds rule: S_MAX is the file's, the largest schedule that is too short for it is in the catalogue and must be killed
+    worst = KV.divsteps_worst()
+    assert M.S_MAX == {"p": worst["s_max_p"], "l": worst["s_max_l"]}
+    for key in ("p", "l"):
+        assert worst["s_max_" + key] == max(e["steps"] for e in worst[key]) and len(worst[key]) == 64
+        need = -(-M.S_MAX[key] // 30) - 1
+        assert any(m.get("rounds") == need and m["family"] == "longest_inversions_" + key and kind(m) == "killed" for m in M.MUTANTS), (key, need)
+
+
+def test_recorded_step_counts_are_the_models():
+    """The counts in tests/golden/divsteps_worst.json, recomputed with the generator's own step model."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_divsteps_worst", os.path.join(HERE, "golden", "gen_divsteps_worst.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    worst = KV.divsteps_worst()
+    for key, mod in (("p", KV.P), ("l", KV.L)):
+        assert all(gen.steps_needed(int(e["a"], 16), mod) == e["steps"] and 0 < int(e["a"], 16) < mod for e in worst[key])
+        assert M.S_MAX[key] > {"p": 524, "l": 518}[key] and M.S_MAX[key] <= 600         # beats plain sampling; within the schedule
+
+
+def test_second_subtraction_is_out_of_reach():
+    """The bound behind the `equivalent` entries of mod_invert_chunk, on the exact register value of the Montgomery multiplier,
+    (T + ((T N') mod R) N) / R with R = 2^261: the running product of a lane stays below 2N for chunks of 2, 7 and 64 rows of
+    the largest five-word patterns (and of seeded patterns next to 2^260), so does every a_j^-1 and every quotient."""
+    import random
+    R = 1 << 261
+    rng = random.Random(KV.SEED + 0x2A)
+    for N in (KV.P, KV.L):
+        NP = (-pow(N, -1, R)) % R
+
+        def mont(a, b):
+            T = a * b
+            v, rem = divmod(T + (T * NP % R) * N, R)
+            assert rem == 0
+            return v
+        big = [(1 << 260) - 1 - d for d in range(4)] + [(1 << 260) - 1 - rng.getrandbits(k) for k in (8, 64, 130, 200, 250, 259)]
+        for c in (2, 7, 64):
+            for trial in range(12):
+                xs = [big[trial % len(big)]] * c if trial < len(big) else [rng.choice(big) for _ in range(c)]
+                acc, pre = R % N, []
+                for x in xs:
+                    pre.append(acc)
+                    acc = mont(acc, x)
+                    assert acc < 2 * N
+                inv = pow(acc % N, -1, N)
+                for x, q in zip(reversed(xs), reversed(pre)):
+                    res = mont(inv, q)
+                    assert res < 2 * N and res % N == pow(x, -1, N)
+                    assert mont((1 << 260) - 1, mont(res, R * R % N)) < 2 * N          # the division form, largest numerator
+                    inv = mont(inv, x)
+                    assert inv < 2 * N
+
+
+@pytest.mark.parametrize("family", sorted(KV.FAMILIES))
+def test_unmutated_copy_passes(built, family):
+    assert failures(built, None, family) == []
+
+
+def test_canary_is_killed(built):
+    m = [m for m in M.MUTANTS if m.get("canary")][0]
+    assert failures(built, m["name"], m["family"]) != []
+
+
+@pytest.mark.parametrize("name", [m["name"] for m in M.MUTANTS])
+def test_planted_defect(built, name):
+    m = BY_NAME[name]
+    k = kind(m)
+    for family in families_of(m):
+        failed = failures(built, name, family)
+        if k == "killed":
+            assert failed != [], "%s survived family %s" % (name, family)
+        else:                                  # equivalent, or a schedule no recorded input exceeds: the claim itself is checked
+            assert failed == [], (name, k, family, failed)

@@ -1,4 +1,5 @@
-// zc_ris_batch.hip.h -- batched Ristretto encoders whose rows share work (zc_ris_double_and_compress).
+// zc_ris_batch.hip.h -- batched Ristretto calls whose rows share work: zc_ris_double_and_compress (below) and
+// zc_ris_lincomb_sum (further down: the weighted sum of all rows as one MSM).
 //
 // out = RistrettoPoint(2 P).compress(): the reference's Double (edwards.rs:579-592) followed by compress
 // (ristretto.rs:398-425), without the square root.  compress pays one (p-5)/8 power per row (about 250 squarings, 265
@@ -28,6 +29,7 @@
 // bytes that depend on their own words only; every launch form decides by canonical values, so the forms agree byte for byte.
 #pragma once
 #include "zc_curve.hip.h"
+#include "zc_msm_plan.h"      // ZC_BLOCK
 
 namespace zc {
 
@@ -152,6 +154,97 @@ ZC_DI void ris_double_compress_chunk(const u64* p, uint8_t* out32, size_t n, siz
     }
 }
 
+// ---------------------------------------------------------------- zc_ris_lincomb_sum: one MSM over all rows, from bytes
+// out = compress(b B + sum_{i, ok_i} sum_j w_ij decompress(E_ij)): three passes prepare ordinary MSM inputs -- 160-byte point
+// records and canonical 40-byte scalars in a workspace of the device slot -- and the MSM pipeline runs on them as it stands.
+//   k_ris_sum_prepare   one lane per (row, term): decode (one inverse-square-root power, bound by the multiplier), the record
+//                       (the identity for an undecodable encoding), w_ij = val(z_i) val(k_ij) mod L, one decode flag
+//   k_ris_sum_rows      one lane per row: ok_i = the AND of the row's flags; a rejected row's scalars become zero (the MSM's
+//                       contract: a zero scalar contributes the identity whatever the record holds); t_i = ok_i ? z_i kB_i : 0
+//   k_sc_sum            b = sum_i t_i mod L: strided partial sums per lane, a tree in LDS per workgroup, one partial per
+//                       workgroup, a second launch of one workgroup over the partials
+// Every scalar and weight is read BY VALUE (sc_muladd_limbs52: val(w) = sum (w_i mod 2^52) 2^(52 i), reduced mod L), so what
+// the MSM receives is canonical and both of its regimes multiply by exactly w_ij.  Addition mod L is associative and every
+// partial is canonical: b does not depend on the launch geometry.
+constexpr size_t SC_SUM_ROWS_PER_LANE = 4;      // first launch of k_sc_sum: a workgroup covers ZC_BLOCK * SC_SUM_ROWS_PER_LANE rows ...
+constexpr size_t SC_SUM_MAX_BLOCKS = 1024;      // ... until this many workgroups; beyond, the lanes stride further
+
+// val(a) val(z) mod L, canonical (z null: val(a) mod L)
+ZC_DI void ris_sum_weighted(u64 (&r)[5], const u64* __restrict__ a, const u64* __restrict__ z)
+{
+    u64 x[5], y[5] = {1, 0, 0, 0, 0};
+    const u64 zero[5] = {0, 0, 0, 0, 0};
+    load5(x, a);
+    if (z) load5(y, z);
+    sc_muladd_limbs52(r, x, y, zero);
+}
+// One (row, term) pair: the encoding's four words -> record, weighted scalar, decode flag.
+ZC_DI void ris_sum_pair(const u64 (&enc)[4], const u64* __restrict__ k, const u64* __restrict__ z, u64* __restrict__ point,
+                        u64* __restrict__ scalar, uint8_t* __restrict__ flag)
+{
+    pt P;
+    const bool dec = ris_decompress(P, enc);
+    pt_store(point, pt_select(dec, P, pt_identity()));
+    u64 w[5];
+    ris_sum_weighted(w, k, z);
+    store5(scalar, w);
+    *flag = dec ? 1 : 0;
+}
+// One row: `flags` and `scalars` are the row's `terms` entries of the workspace; ok and t may be null (t: no base term).
+ZC_DI void ris_sum_row(const uint8_t* __restrict__ flags, size_t terms, u64* __restrict__ scalars, const u64* __restrict__ kb,
+                       const u64* __restrict__ z, uint8_t* __restrict__ ok, u64* __restrict__ t)
+{
+    bool all = true;
+    for (size_t j = 0; j < terms; j++) all &= flags[j] != 0;
+    const u64 zero[5] = {0, 0, 0, 0, 0};
+    if (!all)
+        for (size_t j = 0; j < terms; j++) store5(scalars + 5 * j, zero);
+    if (ok) *ok = all ? 1 : 0;
+    if (t) {
+        u64 w[5];
+        ris_sum_weighted(w, kb, z);                                          // by every lane: the multiplier's path is chosen per wave
+#pragma unroll
+        for (int i = 0; i < 5; i++) w[i] = all ? w[i] : 0;
+        store5(t, w);
+    }
+}
+// the record of the base term's pair: RISTRETTO_BASEPOINT, Z = 1
+ZC_DI void ris_sum_store_basepoint(u64* __restrict__ o)
+{
+    pt B;
+    B.X = fe_const<FP>(ModP::BASE_X_M);
+    B.Y = fe_const<FP>(ModP::BASE_Y_M);
+    B.Z = fe_one_m<FP>();
+    B.T = fe_const<FP>(ModP::BASE_T_M);
+    pt_store(o, B);
+}
+// a + b mod L for canonical a, b
+ZC_DI fe sc_add_canon(const fe& a, const fe& b)
+{
+    fe s = fe_add(a, b);
+    fe_carry(s);
+    return fe_cond_sub_n<ModL>(s);                                           // below 2L
+}
+// lane g of `lanes`: t[g] + t[g + lanes] + ... mod L over n canonical scalars
+ZC_DI fe sc_sum_strided(const u64* __restrict__ t, size_t n, size_t g, size_t lanes)
+{
+    fe acc = fe_zero();
+    for (size_t i = g; i < n; i += lanes) {
+        u64 l[5];
+        load5(l, t + 5 * i);
+        acc = sc_add_canon(acc, fe_from_limbs52(l));
+    }
+    return acc;
+}
+// one level of a workgroup's tree over its lanes' partials: lane `lane` < half takes its partner's (barriers between the levels)
+ZC_DI void sc_sum_tree_step(fe* part, int lane, int half) { part[lane] = sc_add_canon(part[lane], part[lane + half]); }
+ZC_DI void sc_sum_store(u64* __restrict__ out, const fe& s)
+{
+    u64 l[5];
+    fe_to_limbs52(l, s);
+    store5(out, l);
+}
+
 }  // namespace zc
 
 // the kernels: hipcc only (the host emulation of the test tier builds the device functions above with a C++ compiler)
@@ -182,6 +275,38 @@ ZC_KERNEL void k_ris_double_compress_chunked_lone(const u64* p, uint8_t* out32, 
 {
     const size_t lanes = (n + (size_t)c - 1) / (size_t)c, g = gid();
     if (g < lanes) ris_double_compress_chunk<true>(p, out32, n, g, lanes, c);
+}
+
+// zc_ris_lincomb_sum (see above).  One lane per (row, term): in32, k as zc_ris_lincomb lays them out; z null = no weights.
+ZC_KERNEL void k_ris_sum_prepare(const uint8_t* in32, const u64* k, const u64* z, u64* points, u64* scalars, uint8_t* flags, size_t terms, size_t pairs)
+{
+    const size_t g = gid();
+    if (g >= pairs) return;
+    u64 w[4];
+    load_words256(w, in32 + 32 * g);
+    ris_sum_pair(w, k + 5 * g, z ? z + 5 * (g / terms) : nullptr, points + 20 * g, scalars + 5 * g, flags + g);
+}
+// one lane per row; ok null when not requested; kb, t and base_record (the base term's record, written by lane 0) null without a base term
+ZC_KERNEL void k_ris_sum_rows(const uint8_t* flags, u64* scalars, const u64* kb, const u64* z, uint8_t* ok, u64* t, u64* base_record, size_t terms, size_t n)
+{
+    const size_t i = gid();
+    if (i >= n) return;
+    if (i == 0 && base_record) ris_sum_store_basepoint(base_record);
+    ris_sum_row(flags + terms * i, terms, scalars + 5 * terms * i, kb ? kb + 5 * i : nullptr, z ? z + 5 * i : nullptr, ok ? ok + i : nullptr,
+                t ? t + 5 * i : nullptr);
+}
+// out[workgroup] = the sum mod L of the canonical scalars t[g], t[g + lanes], ... of the workgroup's lanes
+ZC_KERNEL void k_sc_sum(const u64* t, size_t n, u64* out)
+{
+    __shared__ fe part[ZC_BLOCK];
+    const int lane = threadIdx.x;
+    part[lane] = sc_sum_strided(t, n, gid(), (size_t)gridDim.x * ZC_BLOCK);
+    __syncthreads();
+    for (int half = ZC_BLOCK / 2; half > 0; half >>= 1) {
+        if (lane < half) sc_sum_tree_step(part, lane, half);
+        __syncthreads();
+    }
+    if (lane == 0) sc_sum_store(out + 5 * (size_t)blockIdx.x, part[0]);
 }
 
 }  // namespace zc

@@ -212,6 +212,7 @@ struct DevState {
     DevBuf scratch[MAX_ARGS];           // staging areas of host batches, one per buffer of the call
     DevBuf bal;                         // lane balancing: 1024 u32 bins + n u32 indices
     DevBuf msm;                         // the MSM workspace: bucket method, or the products and folds of a small shard / batch
+    DevBuf ris_sum;                     // zc_ris_lincomb_sum: the MSM inputs it prepares (records, scalars, flags, base-term partials)
     DevBuf fast;                        // windowed-core tables: ring of wave slots, 256 MB (zc_kernels.hip.h)
     DevBuf ring;                        // tickets and slot flags of the table ring (+ the device address of the error word)
     PinnedMem ring_err;                 // the ring's error word: pinned host memory, written by a wave that gave up
@@ -2064,6 +2065,91 @@ int zc_msm_batch_plan(zc_ctx* ctx, size_t n, size_t batch, int points_aligned16,
     const MsmBucketPlan p = msm_batch_plan(n, batch, points_aligned16 != 0, tune.msm);
     const int32_t v[8] = {p.buckets ? 1 : 0, p.c, p.W, p.affine ? 1 : 0, p.T, p.seg, p.sort.passes, p.buckets ? p.rec_bytes : 0};
     memcpy(out, v, sizeof v);
+    return ZC_OK;
+}
+
+// ---- zerocaf_hip_ext_sum.h (a part of zerocaf_hip_ext.h): the weighted sum of all rows of a wire-format batch as ONE MSM (zc_ris_batch.hip.h)
+// out32 = compress(b B + sum over the accepted rows of w_ij decompress(E_ij)).  Three passes turn the bytes into ordinary MSM
+// inputs in the slot's `ris_sum` workspace -- 160-byte records, canonical scalars, the base term as one more pair -- and
+// msm_on_device runs on them as it stands; the one result point goes through the Ristretto encoder.  Inputs host (staged on
+// device slot 0, as zc_msm_batch stages) or all on one device of the context; synchronous.
+int zc_ris_lincomb_sum(zc_ctx* ctx, const uint8_t* in32, const uint64_t* scalars, size_t terms, const uint64_t* base_scalars, const uint64_t* weights,
+                       uint8_t* out32, uint8_t* ok, size_t n)
+{
+    REQUIRE(in32); REQUIRE(scalars); REQUIRE(out32);
+    if (terms == 0) return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb_sum: terms must be at least 1");
+    // pairs = n terms (+ 1): 31-bit record indices, as msm_on_device requires of a shard
+    if (n > (((size_t)1 << 31) - 2) / terms)
+        return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb_sum: n * terms + 1 must stay below 2^31");
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    const size_t pairs = n * terms, count = pairs + (base_scalars ? 1 : 0);
+    {
+        // the other limits of a shard of `count` pairs, before anything is touched (msm_on_device checks the same)
+        const MsmPlan mp = msm_plan(count, true, ctx->devs[0].tune.msm);
+        if (mp.bad_groups) return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb_sum: ZC_MSM_GROUPS does not add up to the window count of n * terms + 1 pairs");
+        if (count >= zc::MSM_BUCKET_MIN_N && zc::msm_index_limit(0, mp.m, 0))
+            return fail(ZC_ERR_BAD_ARG, "zc_ris_lincomb_sum: n * terms + 1 pairs do not fit 32-bit pair indices");
+    }
+    if (n == 0) {
+        memset(out32, 0, 32);                                    // the empty sum: the identity's encoding
+        return ZC_OK;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {in32, scalars, base_scalars, weights, ok}, "zc_ris_lincomb_sum: ", &owner)) return rc;
+    {
+        Residency r;
+        int d = -1;
+        residency_of(out32, &r, &d);
+        if (r == RES_DEVICE) return fail(ZC_ERR_MIXED_MEM, "zc_ris_lincomb_sum: out32 must be host memory");
+    }
+    DevState& D = owner ? *owner : ctx->devs[0];
+    if (int rc = ring_check(D)) return rc;
+    HIP_TRY(hipSetDevice(D.device));
+    const uint8_t* din = in32;
+    const u64 *dk = scalars, *dkb = base_scalars, *dz = weights;
+    uint8_t* dok = ok;
+    if (!owner) {
+        const void* src[4] = {in32, scalars, base_scalars, weights};
+        const size_t bytes[5] = {pairs * 32, pairs * 40, n * 40, n * 40, n};
+        for (int a = 0; a < 5; a++)
+            if (a < 4 ? src[a] != nullptr : ok != nullptr)
+                if (int rc = D.scratch[a].grow(bytes[a])) return rc;
+        for (int a = 0; a < 4; a++)
+            if (src[a]) HIP_TRY(hipMemcpyAsync(D.scratch[a].as<void>(), src[a], bytes[a], hipMemcpyHostToDevice, D.s()));
+        din = D.scratch[0].as<const uint8_t>();
+        dk = D.scratch[1].as<const u64>();
+        if (base_scalars) dkb = D.scratch[2].as<const u64>();
+        if (weights) dz = D.scratch[3].as<const u64>();
+        if (ok) dok = D.scratch[4].as<uint8_t>();
+    }
+    // the workspace: records and scalars of `count` pairs, a flag per (row, term), t_i per row and the partial sums of the
+    // base term, the 32 bytes of the result
+    const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t blocks = std::min((n + zc::ZC_BLOCK * zc::SC_SUM_ROWS_PER_LANE - 1) / (zc::ZC_BLOCK * zc::SC_SUM_ROWS_PER_LANE), zc::SC_SUM_MAX_BLOCKS);
+    const size_t o_k = up(count * 160), o_f = o_k + up(count * 40), o_t = o_f + up(pairs), o_p = o_t + up(base_scalars ? n * 40 : 0),
+                 o_e = o_p + up(base_scalars ? blocks * 40 : 0);
+    if (int rc = D.ris_sum.grow(o_e + 256)) return rc;
+    char* const ws = D.ris_sum.as<char>();
+    u64 *const wP = (u64*)ws, *const wK = (u64*)(ws + o_k), *const wT = base_scalars ? (u64*)(ws + o_t) : nullptr, *const wPart = (u64*)(ws + o_p);
+    uint8_t *const wF = (uint8_t*)(ws + o_f), *const wE = (uint8_t*)(ws + o_e);
+    hipLaunchKernelGGL(zc::k_ris_sum_prepare, dim3(grid_for(pairs)), dim3(zc::ZC_BLOCK), 0, D.s(), din, dk, dz, wP, wK, wF, terms, pairs);
+    hipLaunchKernelGGL(zc::k_ris_sum_rows, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), (const uint8_t*)wF, wK, dkb, dz, dok, wT,
+                       base_scalars ? wP + 20 * pairs : nullptr, terms, n);
+    if (base_scalars) {
+        // b -> the scalar of the last pair: one workgroup's sum directly, else a partial per workgroup and one workgroup over those
+        u64* const b = wK + 5 * pairs;
+        hipLaunchKernelGGL(zc::k_sc_sum, dim3((unsigned)blocks), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)wT, n, blocks == 1 ? b : wPart);
+        if (blocks > 1) hipLaunchKernelGGL(zc::k_sc_sum, dim3(1), dim3(zc::ZC_BLOCK), 0, D.s(), (const u64*)wPart, blocks, b);
+    }
+    HIP_TRY(hipGetLastError());
+    const u64* res = nullptr;
+    if (int rc = msm_on_device(D, wP, wK, count, &res)) return rc;
+    hipLaunchKernelGGL(zc::k_ris_compress, dim3(1), dim3(zc::ZC_BLOCK), 0, D.s(), res, wE, (size_t)1);
+    HIP_TRY(hipGetLastError());
+    if (!owner && ok) HIP_TRY(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, D.s()));
+    HIP_TRY(hipMemcpyAsync(out32, wE, 32, hipMemcpyDeviceToHost, D.s()));
+    HIP_TRY(hipStreamSynchronize(D.s()));
     return ZC_OK;
 }
 

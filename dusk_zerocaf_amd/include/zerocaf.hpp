@@ -745,6 +745,35 @@ inline std::pair<std::vector<CompressedRistretto>, std::vector<uint8_t>> ris_lin
     for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
     return {out, ok};
 }
+// The weighted sum of all rows as one MSM (zc_ris_lincomb_sum, zerocaf_hip_ext_sum.h through zerocaf_hip_ext.h): compress(b * RISTRETTO_BASEPOINT + sum_i
+// sum_j w_ij * decompress(ess[i][j])) with w_ij = zs[i] * kss[i][j] mod L and b = sum_i zs[i] * bs[i] mod L, every scalar read
+// by value (bs empty: no base term; zs empty: no weights).  A row with an undecodable term has mask 0 and is left out of both
+// sums.  first: the encoding of the sum, second: the accept mask.  A batch verifies when the mask is all ones and the bytes zero.
+inline std::pair<CompressedRistretto, std::vector<uint8_t>> ris_lincomb_sum(const std::vector<std::vector<CompressedRistretto>>& ess,
+                                                                            const std::vector<std::vector<Scalar>>& kss,
+                                                                            const std::vector<Scalar>& bs = {}, const std::vector<Scalar>& zs = {})
+{
+    if (ess.size() != kss.size() || (!bs.empty() && bs.size() != ess.size()) || (!zs.empty() && zs.size() != ess.size()))
+        throw std::invalid_argument("ris_lincomb_sum: size mismatch");
+    const size_t n = ess.size(), t = n ? ess[0].size() : 1;
+    std::vector<uint8_t> e(n * t * 32 + 1), ok(n);                  // (one spare element: data() is never null, and n == 0 is the empty sum)
+    std::vector<uint64_t> k(n * t * 5 + 1), b(bs.size() * 5), z(zs.size() * 5);
+    for (size_t i = 0; i < n; i++) {
+        if (ess[i].size() != t || kss[i].size() != t) throw std::invalid_argument("ris_lincomb_sum: rows of different lengths");
+        for (size_t j = 0; j < t; j++) {
+            std::memcpy(&e[32 * (i * t + j)], ess[i][j].bytes.data(), 32);
+            std::memcpy(&k[5 * (i * t + j)], kss[i][j].l.data(), 40);
+        }
+        if (!bs.empty()) std::memcpy(&b[5 * i], bs[i].l.data(), 40);
+        if (!zs.empty()) std::memcpy(&z[5 * i], zs[i].l.data(), 40);
+    }
+    CompressedRistretto out;
+    uint8_t o[32];
+    Backend::check(zc_ris_lincomb_sum(Backend::ctx(), e.data(), k.data(), t, bs.empty() ? nullptr : b.data(), zs.empty() ? nullptr : z.data(), o, ok.data(), n),
+                   "zc_ris_lincomb_sum");
+    std::memcpy(out.bytes.data(), o, 32);
+    return {out, ok};
+}
 // {regime (0 = scalar multiplications + folds, 1 = buckets), c, W, affine, run length, segment buckets, sort passes, record
 // stride bytes} of a batch of `batch` instances of n pairs
 inline std::array<int32_t, 8> msm_batch_plan(size_t n, size_t batch, bool points_aligned16 = true)

@@ -550,8 +550,55 @@ ZC_DI bool fp_legendre(const fe& a, int max_rounds = JACOBI_MAX_ROUNDS)
     return res;
 }
 
+// ---------------------------------------------------------------- multiplication by the curve constant
+// d x mod p without a field multiplication.  d = -126296/126297 = 1/m - 1 with m = MD = 126297 (17 bits, odd), so
+// d x = x/m - x, and x/m mod p is an exact integer division: with u = -x p^-1 (mod m) the number x + u p is a multiple of m.
+//   S  = sum x_i MD_K[i] = u (mod m), nine multiply-adds; a Barrett quotient brings it to u < 2^20 (u need not be below m);
+//   z' = x + u p + m is divided by m from the low limb up, Montgomery fashion: v_i = -z'_i / m (mod 2^29) cancels limb i, so
+//        z' + V m = m 2^261, i.e. z'/m + V = 2^261, and y = z'/m - 1 = (x + u p)/m is the limb-wise complement of V.  The
+//        offset m keeps z' positive for x = 0 (T of the identity and of the 2-torsion rows), where y must come out 0;
+//   the result is y + (4N - x), left without a carry pass.
+// The same residue as mont_mul(D_M, x) whatever the domain of x, so every canonicalised limb downstream is unchanged.
+// 33 multiplier-class instructions (9 + 2 + 5 + 9 + 8) against the 160 of a Montgomery multiplication.
+// Input R-class.  Output: value < 8.1N + 4N < 13N, limbs < 2^29 + 2^30, top limb < 2^24 -- a multiplier operand only, against
+// a partner with limbs < 2^29 (R-class): 9 * 1.5 * 2^59 + reduction terms < 2^64 as for fe_sub_lazy.
+ZC_DI fe fp_mul_d(const fe& x)
+{
+    typedef ModP F;
+    for (int i = 0; i < 8; i++) ZC_ASSERT(x.v[i] < (1u << 29));
+    ZC_ASSERT(x.v[8] <= (3u << F::TOPSHIFT));
+    u64 s = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        s += (u64)x.v[i] * F::MD_K[i];
+        ZC_PIN(s);
+    }
+    const u32 q = (u32)(((u64)(u32)(s >> 18) * F::MD_BARRETT) >> 32);      // floor(s / 4m), at most 4 too small
+    const u32 u = (u32)s - q * (4u * F::MD);
+    ZC_ASSERT((s >> 18) < (1ull << 32) && u < (1u << 20) && (s - u) % F::MD == 0);
+    fe r;
+    u32 carry = F::MD;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        u64 acc = x.v[i] + carry;
+        if (i < 5) acc += (u64)u * F::N[i];
+        if (i == 8) acc += u << F::TOPSHIFT;                  // N[5..7] == 0; of the top limb only the low 29 bits count
+        const u32 v = ((u32)acc * F::MD_NMINV) & M29;
+        if (i < 8) {
+            acc += (u64)v * F::MD;                            // low 29 bits are now zero
+            carry = (u32)(acc >> 29);                         // acc < 2^50
+        }
+#if defined(ZC_CHECK_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
+        if (i == 8) ZC_ASSERT((x.v[8] + carry + ((u64)u << F::TOPSHIFT) + (u64)v * F::MD) >> 29 == F::MD);   // z' + V m = m 2^261
+#endif
+        r.v[i] = (v ^ M29) + (F::BIAS[i] - x.v[i]);
+    }
+    ZC_ASSERT(r.v[8] < (1u << 24));
+    return r;
+}
+
 // ---------------------------------------------------------------- points
-ZC_DI pt pt_identity()                                            // edwards.rs:381-391
+ZC_DI pt pt_identity()                                           // edwards.rs:381-391
 {
     pt r;
     r.X = fe_zero();
@@ -582,7 +629,7 @@ ZC_DI pt pt_add(const pt& p, const pt& q)
     auto fp_mul = [](const fe& x, const fe& y) { return ILP ? mont_mul_ilp<FP>(x, y) : mont_mul<FP>(x, y); };
     const fe M = fp_mul(fp_sub(p.Y, p.X), fp_sub(q.Y, q.X));          // operands < 7N: M < 2N
     const fe P = fp_mul(fe_add(p.Y, p.X), fe_add(q.Y, q.X));          // operands < 6N: P < 2N
-    const fe C = fp_mul(fp_mul(fe_const<FP>(ModP::D_M), p.T), q.T);
+    const fe C = fp_mul(fp_mul_d(p.T), q.T);
     const fe D = fp_mul(p.Z, q.Z);
     const fe E = fe_sub_half<FP>(P, M);
     const fe H = fp_sub(P, E);
@@ -608,7 +655,7 @@ ZC_DI pt pt_add_plain(const pt& p, const pt& q)         // plain R-class coordin
     auto fp_mul = [](const fe& x, const fe& y) { return ILP ? mont_mul_ilp<FP>(x, y) : mont_mul<FP>(x, y); };
     const fe M = fp_mul(fp_sub(p.Y, p.X), fp_sub(q.Y, q.X));
     const fe P = fp_mul(fe_add(p.Y, p.X), fe_add(q.Y, q.X));
-    const fe C = fp_mul(fp_mul(fe_const<FP>(ModP::D_M), p.T), q.T);
+    const fe C = fp_mul(fp_mul_d(p.T), q.T);
     const fe D = fp_mul(p.Z, q.Z);
     const fe E = fe_sub_half<FP>(P, M);
     const fe H = fp_sub(P, E);
@@ -711,7 +758,7 @@ ZC_DI ptm ptm_add(const ptm& p, const ptm& q)          // same values as pt_add
     auto fp_mul = [](const fe& x, const fe& y) { return ILP ? mont_mul_ilp<FP>(x, y) : mont_mul<FP>(x, y); };
     const fe M = fp_mul(p.Ym, q.Ym);
     const fe P = fp_mul(p.Yp, q.Yp);
-    const fe C = fp_mul(fp_mul(fe_const<FP>(ModP::D_M), p.T), q.T);
+    const fe C = fp_mul(fp_mul_d(p.T), q.T);
     const fe D = fp_mul(p.Z, q.Z);
     const fe E = fe_sub_half<FP>(P, M);
     const fe H = fe_sub_lazy<FP>(P, E);
@@ -882,7 +929,7 @@ ZC_DI ptm ptm_add_stash(const ptm& lhs, const ptm& N, bool from_stash, const STA
 {
     const fe M = mont_mul<FP>(lhs.Ym, fe_select(from_stash, S.get(0), N.Ym));
     const fe P = mont_mul<FP>(lhs.Yp, fe_select(from_stash, S.get(1), N.Yp));
-    const fe C = mont_mul<FP>(mont_mul<FP>(fe_const<FP>(ModP::D_M), lhs.T), fe_select(from_stash, S.get(3), N.T));
+    const fe C = mont_mul<FP>(fp_mul_d(lhs.T), fe_select(from_stash, S.get(3), N.T));
     const fe D = mont_mul<FP>(lhs.Z, fe_select(from_stash, S.get(2), N.Z));
     const fe E = fe_sub_half<FP>(P, M);
     const fe H = fe_sub_lazy<FP>(P, E);

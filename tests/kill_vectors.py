@@ -8,6 +8,10 @@ A family is a list of `Case`s built once: an abstract operation, input rows, exp
 Python integers (oracle/pymodel.py) except the two left-to-right scalar multiplications, whose limbs come from the C oracle.
 `run(family, backend)` returns the comparisons that failed.  A backend answers `call(case)` with the outputs, or None where
 it has no such operation: `EmulBackend` wraps one host-emulation library (tests/emul/*.cpp), `EngineBackend` an Engine.
+
+Operations with several launch forms: `Form` names one, `EngineBackend(form=...)` runs only the cases that have it, and
+`packed` reorders a `mulmod` case so that whole waves take one product form (tests/test_kill_vector_waves.py holds the wave
+model, tests/test_gpu_kill_vector_forms.py the forms).  `Case.bad_rows` names the rows behind a failed comparison.
 """
 import ctypes as C
 import importlib.util
@@ -111,9 +115,9 @@ class Case:
         c.want = tuple(np.ascontiguousarray(w[idx]) for w in self.want)
         return c
 
-    def mismatches(self, got):
-        """Indices of the outputs that differ from `want`."""
-        bad = []
+    def _compared(self, got):
+        """(output index, got, want, row numbers) per output, as they are compared: points as affine limbs under cmp="group",
+        the rows the accept flag rejects dropped from every output but the flag."""
         keep = None
         if self.ok is not None:
             keep = np.asarray(self.want[self.ok]).astype(bool)
@@ -122,11 +126,91 @@ class Case:
             if self.cmp == "group" and i == 0:
                 g = affine_rows(g)
             g = g.reshape(w.shape) if g.size == w.size else g
+            at = np.arange(len(w))
             if keep is not None and i != self.ok:
-                g, w = g[keep], w[keep]
-            if g.shape != w.shape or not np.array_equal(g.astype(w.dtype), w):
-                bad.append(i)
-        return bad
+                g, w, at = g[keep], w[keep], at[keep]
+            yield i, g, w, at
+
+    def mismatches(self, got):
+        """Indices of the outputs that differ from `want`."""
+        return [i for i, g, w, _ in self._compared(got) if g.shape != w.shape or not np.array_equal(g.astype(w.dtype), w)]
+
+    def bad_rows(self, got, output=None):
+        """Sorted indices of the rows that differ from `want` in any output (or in output `output` alone), by the rules of
+        `mismatches`; an output of another shape than expected counts with every row it is compared on."""
+        bad = set()
+        for i, g, w, at in self._compared(got):
+            if output is not None and i != output:
+                continue
+            if g.shape != w.shape:
+                bad.update(at.tolist())
+            else:
+                differ = (g.astype(w.dtype) != w).reshape(len(w), -1).any(axis=1)
+                bad.update(at[differ].tolist())
+        return sorted(bad)
+
+
+# ------------------------------------------------------------------ the product form of a wave (mulmod cases)
+WAVE = 64
+TOPBIT = {0: 252, 1: 249}                    # modl -> F::TOPBIT of zc_arith.hip.h: operands below 2^TOPBIT take the one-pass product
+MAX_LEVEL = 3
+
+
+def mulmod_levels(case, which):
+    """Per row of a mulmod case, how far its operands reach above 2^TOPBIT, read from the limbs as fe_mulmod_limbs52 /
+    fe_sqrmod_limbs52 do (bits of limb 4 from TOPBIT - 208 on; the product ORs both operands, the square looks at `a` alone):
+    0 = eligible for the one-pass form, k = the highest set bit is TOPBIT + k - 1 (capped at MAX_LEVEL).  which: "mul" / "sq"."""
+    assert case.op == "mulmod" and which in ("mul", "sq")
+    a, b = (np.asarray(x, dtype=np.uint64) for x in case.ins)
+    top = (a[:, 4] | b[:, 4]) if which == "mul" else a[:, 4]
+    top = (top & np.uint64(M52)) >> np.uint64(TOPBIT[case.params["modl"]] - 208)
+    return np.array([min(int(t).bit_length(), MAX_LEVEL) for t in top])
+
+
+def wave_levels(levels):
+    """The wave model: a wave is WAVE consecutive rows of one call, and the device chooses the product form with a ballot over
+    it.  Per row, the highest level in the row's wave -- the wave takes the one-pass form exactly when that is 0."""
+    levels = np.asarray(levels)
+    out = np.empty_like(levels)
+    for w in range(0, len(levels), WAVE):
+        out[w:w + WAVE] = levels[w:w + WAVE].max()
+    return out
+
+
+def _pad_wave(idx):
+    """idx repeated from its start up to a whole number of waves."""
+    idx = list(idx)
+    return idx + [idx[j % len(idx)] for j in range(-len(idx) % WAVE)]
+
+
+def pack_order(levels, packing):
+    """Row order of one packing of a mulmod case (indices into the case, every row at least once).
+    "one-pass": the rows of each level in whole waves of their own, the last wave of a level filled with repeats of that
+    level's rows -- so every eligible row (level 0) sits in an all-eligible wave, the ineligible rows follow in waves without
+    an eligible row, and a wave of rows just above 2^TOPBIT holds no row further up (a threshold moved by a bit shows there).
+    "two-pass": 63 eligible rows and one ineligible row per wave, the ineligible rows taking turns; the last wave holds what
+    is left of both -- so every eligible row meets the two Montgomery passes."""
+    levels = np.asarray(levels)
+    elig, inel = np.flatnonzero(levels == 0).tolist(), np.flatnonzero(levels > 0).tolist()
+    assert elig and inel
+    if packing == "one-pass":
+        return np.array(sum((_pad_wave(np.flatnonzero(levels == lv)) for lv in range(MAX_LEVEL + 1) if (levels == lv).any()), []))
+    assert packing == "two-pass"
+    order, used = [], 0
+    for s in range(0, len(elig), WAVE - 1):
+        order += elig[s:s + WAVE - 1] + [inel[used % len(inel)]]
+        used += 1
+    return np.array(order + inel[used:])
+
+
+def packed(case, which, packing):
+    """(the mulmod case reordered by pack_order for the product ("mul") or the square ("sq"), `want` alike; the order)."""
+    order = pack_order(mulmod_levels(case, which), packing)
+    c = Case.__new__(Case)
+    c.__dict__.update(case.__dict__)
+    c.ins = tuple(np.ascontiguousarray(x[order]) for x in case.ins)
+    c.want = tuple(np.ascontiguousarray(w[order]) for w in case.want)
+    return c, order
 
 
 def run(family, backend, cases=None):
@@ -342,13 +426,35 @@ class EmulBackend:
 
 
 # ------------------------------------------------------------------ the Engine backend (GPU tier)
+STRICT_OPS = ("ed_scalar_mul", "sm_tiles")
+
+
+class Form:
+    """One launch form of an operation that has several (tests/test_gpu_kill_vector_forms.py holds the table).  ops: the case
+    operations it is a form of.  lo, hi: the batch sizes that reach it (inclusive).  env: the ZC_* knobs the engine's context
+    must have been created under.  hooks: the engine runs the test-hooks build.  staged: whether every launch of the call takes
+    its LDS-staged kernel (None: the operation has no such kernel) -- checked against the test build's launch counter where
+    the engine has one.  misalign: rows 8 bytes off a 16-byte boundary.  small: the independent-chain strict kernel, the one
+    how="small" names."""
+
+    def __init__(self, name, ops, lo=1, hi=1 << 40, env=None, hooks=False, staged=None, misalign=False, small=False):
+        self.name, self.ops, self.lo, self.hi, self.env = name, tuple(ops), lo, hi, dict(env or {})
+        self.hooks, self.staged, self.misalign, self.small = hooks, staged, misalign, small
+
+
 class EngineBackend:
     """The same cases through the C ABI.  chunk: the ZC_INV_CHUNK the engine's context was created under (None: the library's
     default) -- an inversion case runs on the engine whose chunk it names, every other case on the default engine only.
-    device: inputs as torch tensors on the GPU.  misalign: host arrays that start 8 bytes off a 16-byte boundary."""
+    device: inputs as torch tensors on the GPU.  misalign: arrays that start 8 bytes off a 16-byte boundary.
+    form: a `Form` -- only the cases of its operations run (the others have one form: None), at a batch size inside its range,
+    on device tensors so that one call is one launch; `how="small"` runs where the form is that kernel, and `counted` collects
+    (op, staged launches counted by the test build or None) per call."""
 
-    def __init__(self, engine, chunk=None, device=False, misalign=False):
-        self.e, self.chunk, self.device, self.misalign = engine, chunk, device, misalign
+    def __init__(self, engine, chunk=None, device=False, misalign=False, form=None):
+        self.e, self.chunk, self.device, self.misalign, self.form = engine, chunk, device, misalign, form
+        self.counted = []
+        if form is not None:
+            self.device, self.misalign = True, form.misalign
 
     def _in(self, a):
         if a is None:
@@ -357,6 +463,12 @@ class EngineBackend:
         if self.device:
             import torch
             t = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
+            if self.misalign:
+                raw = torch.empty(t.numel() * t.element_size() + 16, dtype=torch.uint8, device="cuda")
+                view = raw[8:8 + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+                view.copy_(t)
+                assert raw.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 8 and view.is_contiguous()
+                return view
             return t.cuda()
         if self.misalign:
             raw = np.zeros(a.nbytes + 32, dtype=np.uint8)
@@ -367,6 +479,14 @@ class EngineBackend:
             return view
         return a
 
+    @classmethod
+    def reach(cls, case):
+        """Indices of the outputs of `case` that an EngineBackend of some configuration (chunk, form) returns: () where the C ABI
+        has no such operation or setting -- digit strings, step counts, a lone-chunk multiplier, a Jacobi schedule of its own."""
+        if not hasattr(cls, "op_" + case.op) or case.params.get("lone") or (case.op == "fe_legendre" and case.params.get("rounds", 40) != 40):
+            return ()
+        return (0,) if case.op == "sm_tiles" else tuple(range(len(case.want)))
+
     @staticmethod
     def _host(x):
         if hasattr(x, "cpu"):
@@ -375,9 +495,16 @@ class EngineBackend:
                 x = x.view(np.uint64)
         return x
 
+    def takes(self, case):
+        """Under a form: is `case` one of the form's operations in a setting that has that form?"""
+        if self.form is None:
+            return True
+        how = case.params.get("how", "strict")
+        return case.op in self.form.ops and (case.op not in STRICT_OPS or how == "strict" or (how == "small" and self.form.small))
+
     def call(self, case):
         fn = getattr(self, "op_" + case.op, None)
-        if fn is None:
+        if fn is None or not self.takes(case):
             return None
         inv = case.op in ("fe_invert", "fe_div", "ed_to_affine", "sc_invert")
         c = case.params.get("c", 0)
@@ -386,9 +513,15 @@ class EngineBackend:
                 return None
         elif self.chunk is not None:
             return None
+        if self.form is not None:
+            n = len(case.ins[0])
+            assert self.form.lo <= n <= self.form.hi, "%s: %d rows do not reach the form '%s'" % (case.label(), n, self.form.name)
+        counter = getattr(self.e.lib, "zc_test_staged_launches", None)
+        c0 = counter(self.e.ctx) if counter else 0
         got = fn(*[self._in(x) for x in case.ins], **{k: v for k, v in case.params.items() if k not in ("c", "lone")})
         if got is None:
             return None
+        self.counted.append((case.op, counter(self.e.ctx) - c0 if counter else None))
         return tuple(self._host(x) for x in (got if isinstance(got, tuple) else (got,)))
 
     def op_mulmod(self, a, b, modl):
@@ -419,8 +552,8 @@ class EngineBackend:
         return self.e.ed_add(a, b) if mode == 0 else self.e.ed_sub(a, b) if mode == 1 else self.e.ed_double(a)
 
     def op_ed_scalar_mul(self, pts, k, how):
-        if how == "small":
-            return None
+        if how == "small":                                  # the strict call at a batch size that takes k_ed_scalar_mul_small
+            return self.e.ed_scalar_mul(pts, k, flags=0) if self.form is not None and self.form.small else None
         return self.e.ed_scalar_mul(pts, k, flags={"strict": 0, "ltr": 1, "naf": 2, "fast": 16}[how])
 
     def op_sm_tiles(self, pts, k, steps=None): return self.e.ed_scalar_mul(pts, k, flags=0)

@@ -2,11 +2,15 @@
 where the header promises only that (the windowed scalar multiplication, the linear combinations, mul_base).
 
 The CPU tier (tests/test_mutants_emul.py) shows that these rows catch a wrong line in the headers' host build; here the same
-rows meet the kernels, in the launch forms the operations have: the families as built and tiled to 1, 63, 65, 257 and 300
-rows, host arrays, device tensors and host arrays that start 8 bytes off a 16-byte boundary, and for the shared inversions
-ZC_INV_CHUNK = 2, 7, 64 next to the default one row per lane.  The worst-case inversion inputs fill their batches, so every
-position of every chunk holds one.  Operations that exist only in the emulation (digit strings, step counts, the
-independent-chain multiplier on its own) are left to the CPU tier."""
+rows meet the kernels in the launch forms that batches of at most 300 rows reach: the families as built and tiled to 1, 63,
+65, 257 and 300 rows, host arrays, device tensors and host arrays that start 8 bytes off a 16-byte boundary, and for the shared
+inversions ZC_INV_CHUNK = 2, 7, 64 next to the default one row per lane.  The worst-case inversion inputs fill their batches,
+so every position of every chunk holds one.  At these sizes the strict scalar multiplication is always the four-lanes-per-row
+kernel (k_ed_scalar_mul_quad), the point additions and the stand-alone products always run per lane, and the products' waves
+are whatever 64 consecutive rows of a family happen to be.  The other forms -- the independent-chain, workgroup and
+persistent-wave strict kernels and ZC_SCHED, the staged point and 40-byte kernels, and the products with their rows packed so
+that whole waves take the one-pass or the two-pass form -- are in tests/test_gpu_kill_vector_forms.py.  Operations that exist
+only in the emulation (digit strings, step counts, the interleaved multiplier) are left to the CPU tier."""
 import pytest
 
 from tests import kill_vectors as KV

@@ -165,6 +165,64 @@ def test_canary_is_killed(built):
     assert failures(built, m["name"], m["family"]) != []
 
 
+def killing(built, name, family):
+    """[(case, outputs, indices of the outputs that differ)] of the comparisons the changed build fails in one family."""
+    backend = KV.EmulBackend(C.CDLL(built[name][KV.FAMILIES[family].lib]))
+    out = []
+    for case in KV.FAMILIES[family].cases():
+        got = backend.call(case)
+        bad = case.mismatches(got) if got is not None else []
+        if bad:
+            out.append((case, got, bad))
+    return out
+
+
+ONE_PASS_ONLY = ("plain_fold_", "from_limbs52_shl_low_limb", "to_limbs52_shr_offset")       # lines only the one-pass product runs
+
+
+def test_killing_rows_are_carried(built):
+    """What kills a defect here must be what the GPU tier can carry into every launch form (tests/test_gpu_kill_vector_forms.py
+    tiles the rowwise cases).  Per killed entry, from the emulation's failed comparisons and the rows that differ:
+      * if a failed comparison is one the C ABI reaches (kill_vectors.EngineBackend.reach: the operation exists there and a
+        differing output is one it returns), at least one such case is rowwise;
+      * entries without any are listed -- found by that rule, not kept by hand: their killers are digit strings, effective
+        scalars, step counts, the interleaved multiplier or a Jacobi schedule of three rounds, which exist in the emulation only;
+      * a defect killed through `mulmod`: the emulation chooses the product form per row, the device per wave, so every
+        killing row must sit, in the one-pass packing, in a wave whose rows all reach as far above 2^TOPBIT as it does (the
+        ballot then decides as the row alone would) -- eligible killing rows in all-eligible waves; the defects in lines only
+        the one-pass product runs must have such rows."""
+    problems, emulation_only = [], []
+    for m in M.MUTANTS:
+        if kind(m) != "killed":
+            continue
+        failed = killing(built, m["name"], m["family"])
+        assert failed, m["name"]
+        reached = [(case, got, bad) for case, got, bad in failed if set(bad) & set(KV.EngineBackend.reach(case))]
+        if not reached:
+            emulation_only.append("%s (%s)" % (m["name"], ", ".join(sorted({case.label() for case, _, _ in failed}))))
+            continue
+        if not any(case.rowwise for case, _, _ in reached):
+            problems.append("%s: no rowwise case among %s" % (m["name"], [case.label() for case, _, _ in reached]))
+        eligible_killers = 0
+        for case, got, bad in reached:
+            if case.op != "mulmod":
+                continue
+            for output, which in ((0, "mul"), (1, "sq")):
+                rows = case.bad_rows(got, output)
+                lv = KV.mulmod_levels(case, which)
+                order = KV.pack_order(lv, "one-pass")
+                as_alone = set(order[KV.wave_levels(lv[order]) == lv[order]].tolist())
+                eligible_killers += sum(1 for r in rows if lv[r] == 0)
+                if not set(rows) <= as_alone:
+                    problems.append("%s: %s rows %s of %s sit in no wave that decides as they do" % (m["name"], which, sorted(set(rows) - as_alone), case.label()))
+        if m["name"].startswith(ONE_PASS_ONLY) and not eligible_killers:
+            problems.append("%s: no killing row is eligible for the one-pass product" % m["name"])
+    print("killed in the emulation only (no failed comparison the C ABI reaches):")
+    for line in emulation_only:
+        print("    " + line)
+    assert problems == []
+
+
 @pytest.mark.parametrize("name", [m["name"] for m in M.MUTANTS])
 def test_planted_defect(built, name):
     m = BY_NAME[name]

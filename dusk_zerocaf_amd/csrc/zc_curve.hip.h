@@ -921,28 +921,9 @@ ZC_DI bool pt_doubling_identities_hold(const pt& p, const ptm& n)
     const fe rhs = fe_add(mont_sqr<FP>(p.Z), mont_mul<FP>(fe_const<FP>(ModP::D_M), mont_sqr<FP>(p.T)));
     return fp_eq(rhs, lhs) && fp_eq(mont_mul<FP>(p.T, p.Z), mont_mul<FP>(p.X, p.Y));
 }
-// ptm_add(lhs, rhs) with rhs = N, or the lane's stashed addend read coordinate by coordinate next to the multiplication
-// that consumes it (never a fourth live point; every lane reads its slot, no branch).
+// The generic step is ptm_add(lhs, rhs) with rhs = N, or the lane's stashed addend read coordinate by coordinate next to the
+// multiplication that consumes it (never a fourth live point; every lane reads its slot, no branch).
 // STASH: fe get(int coordinate) / void put(int coordinate, const fe&), coordinates 0..3 = Ym, Yp, Z, T.
-template <class STASH>
-ZC_DI ptm ptm_add_stash(const ptm& lhs, const ptm& N, bool from_stash, const STASH& S)
-{
-    const fe M = mont_mul<FP>(lhs.Ym, fe_select(from_stash, S.get(0), N.Ym));
-    const fe P = mont_mul<FP>(lhs.Yp, fe_select(from_stash, S.get(1), N.Yp));
-    const fe C = mont_mul<FP>(fp_mul_d(lhs.T), fe_select(from_stash, S.get(3), N.T));
-    const fe D = mont_mul<FP>(lhs.Z, fe_select(from_stash, S.get(2), N.Z));
-    const fe E = fe_sub_half<FP>(P, M);
-    const fe H = fe_sub_lazy<FP>(P, E);
-    const fe F = fe_sub_lazy<FP>(D, C);
-    const fe G = fe_add(D, C);
-    const fe X3 = mont_mul<FP>(E, F), Y3 = mont_mul<FP>(G, H);
-    ptm o;
-    o.Ym = fp_sub(Y3, X3);
-    o.Yp = fe_add(Y3, X3);
-    o.Z = mont_mul<FP>(F, G);
-    o.T = mont_mul<FP>(E, H);
-    return o;
-}
 // Per-lane state of the schedule.  A lane performs exactly double_and_add's operations in its order -- Q += N_i for the set
 // bits i ascending, N_i the i-th iterate of `self + self`, the first addition identity + N literal, the final doubling skipped
 // -- but an addition may wait in the lane's one stash slot S while N moves on:
@@ -983,22 +964,66 @@ ZC_DI void sm_lane_advance(sm_lane& L, const u32* __restrict__ sk, int stride)
     if ((L.pos & 31) == 0) L.cur = sk[(L.pos >> 5) * stride];
     L.taken = false;
 }
+// The result of a generic step, one operation short of final in Ym and Yp, written into `dst` (Q or N) for the lanes of the
+// enclosing branch: the last operation of a limb -- the mask of fp_sub's carry pass, fe_add's addition -- is emitted once per
+// destination, straight into the destination's registers, instead of once into a temporary that two register moves per
+// limb then distribute.  The mask and a zero addend are opaque scalars of the branch: that keeps the two copies from being
+// merged and hoisted back in front of the branches, and costs no vector instruction.  Z and T leave the multiplier final and
+// are copied.  d: Y3 - X3 + 4N after the carry additions, limbs unmasked (fe_sub's values before its masks).
+ZC_DI void sm_g_commit(ptm& dst, const u32 (&d)[9], const fe& Y3, const fe& X3, const fe& Z3, const fe& T3)
+{
+    u32 mask = M29, zero = 0;
+    ZC_OPAQUE(mask);
+    ZC_OPAQUE(zero);
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        dst.Ym.v[i] = i < 8 ? d[i] & mask : d[i];
+        dst.Yp.v[i] = Y3.v[i] + X3.v[i] + zero;
+    }
+    dst.Z = Z3;
+    dst.T = T3;
+}
+// No early return for a retired lane: `add` and `dbl` are both false there, nothing is committed and the lane's state stays
+// as it is (it computes N + N on the side; the loop runs only while some lane of the wave is active).  Q and N so keep
+// one register home around the whole step loop.
 template <class STASH>
 ZC_DI void sm_g_step(sm_lane& L, ptm& N, ptm& Q, const STASH& S, const u32* __restrict__ sk, int stride)
 {
-    if (!L.active) return;
-    const bool from_stash = L.has_stash;
-    const bool add = from_stash || sm_bit_pending(L);
-    const ptm r = ptm_add_stash(ptm_select(add, Q, N), N, from_stash, S);
+    const bool from_stash = L.active && L.has_stash;
+    const bool add = L.active && (L.has_stash || sm_bit_pending(L));
+    const bool dbl = L.active && !add;
+    u32 d[9];
+    fe X3, Y3, Z3, T3;
+    {
+        const ptm lhs = ptm_select(add, Q, N);
+        const fe M = mont_mul<FP>(lhs.Ym, fe_select(from_stash, S.get(0), N.Ym));
+        const fe P = mont_mul<FP>(lhs.Yp, fe_select(from_stash, S.get(1), N.Yp));
+        const fe C = mont_mul<FP>(fp_mul_d(lhs.T), fe_select(from_stash, S.get(3), N.T));
+        const fe D = mont_mul<FP>(lhs.Z, fe_select(from_stash, S.get(2), N.Z));
+        const fe E = fe_sub_half<FP>(P, M);
+        const fe H = fe_sub_lazy<FP>(P, E);
+        const fe F = fe_sub_lazy<FP>(D, C);
+        const fe G = fe_add(D, C);
+        X3 = mont_mul<FP>(E, F);
+        Y3 = mont_mul<FP>(G, H);
+        Z3 = mont_mul<FP>(F, G);
+        T3 = mont_mul<FP>(E, H);
+    }
+    for (int i = 0; i < 9; i++) ZC_ASSERT(X3.v[i] <= FP::BIAS[i] && Y3.v[i] < (1u << 31));      // fp_sub(Y3, X3)'s operands
+#pragma unroll
+    for (int i = 0; i < 9; i++) d[i] = Y3.v[i] + (FP::BIAS[i] - X3.v[i]);
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k + 1] += d[k] >> 29;
     if (add) {
-        Q = r;
+        sm_g_commit(Q, d, Y3, X3, Z3, T3);
         if (!from_stash) L.taken = true;
         L.has_stash = false;
-    } else {
-        N = r;
+    }
+    if (dbl) {
+        sm_g_commit(N, d, Y3, X3, Z3, T3);
         sm_lane_advance(L, sk, stride);
     }
-    L.active = L.pos < L.nbits - 1 || !L.taken;                     // the top bit is set: its addition retires the lane
+    L.active = L.active && (L.pos < L.nbits - 1 || !L.taken);       // the top bit is set: its addition retires the lane
 }
 template <class STASH>
 ZC_DI void sm_d_step(sm_lane& L, ptm& N, STASH& S, const u32* __restrict__ sk, int stride)

@@ -922,9 +922,12 @@ ZC_KERNEL void k_ed_scalar_mul_pw(const u64* p, const u64* k, u64* out, const u3
         ptm N = ptm_from_pt(P), Q = ptm_from_pt(pt_identity());
         const bool d_ok = wave_all(!valid || pt_doubling_identities_hold(P, N));
         sm_lane L = sm_lane_init(skw, valid ? nbits : 0);
-        while (wave_any(L.active)) {
+        // The loop leaves right after a generic step (a doubling step retires no lane): tested at the head instead, Q would
+        // reach the epilogue from the loop header and be copied out of its registers and back once per step.
+        if (wave_any(L.active)) for (;;) {
             sm_g_step(L, N, Q, S, skw, 64);
-            if (d_ok && sm_tile_wants_d_step(wave_any(L.active), wave_any(sm_at_top(L)))) sm_d_step(L, N, S, skw, 64);
+            if (!wave_any(L.active)) break;
+            if (d_ok && sm_tile_wants_d_step(true, wave_any(sm_at_top(L)))) sm_d_step(L, N, S, skw, 64);
         }
         if (valid) pt_store(out + 20 * own, ptm_to_pt(Q));
     }

@@ -1836,6 +1836,14 @@ ZC_DI pt ris_elligator(const fe& r0)
     o.T = fp_mul(W0, W2);
     return o;
 }
+// from_uniform_bytes (ristretto.rs:493-507) on the 64 bytes as two little-endian 256-bit halves already in registers: two
+// Elligator maps, one addition -- the sequence of k_ris_from_uniform_bytes, which loads each half from memory right before its map.
+ZC_DI pt ris_from_uniform_words(const u64 (&lo)[4], const u64 (&hi)[4])
+{
+    const pt R1 = ris_elligator(mont_to<FP>(fe_from_words256(lo)));
+    const pt R2 = ris_elligator(mont_to<FP>(fe_from_words256(hi)));
+    return pt_add(R1, R2);
+}
 // curve equation in projective form (edwards.rs:733-748): (a X^2 + Y^2) Z^2 == Z^4 + d X^2 Y^2
 ZC_DI bool ed_is_valid(const pt& p)
 {

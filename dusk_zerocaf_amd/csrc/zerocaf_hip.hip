@@ -1437,15 +1437,36 @@ int zc_host_unregister(void* ptr)
     return ZC_OK;
 }
 
-int zc_ctx_synchronize(zc_ctx* ctx)
+// Waits for every slot's stream and reports the ring's error word.  The caller holds ctx->mu.
+static int drain_slots_locked(zc_ctx* ctx)
 {
-    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     for (auto& ds : ctx->devs) {
         HIP_TRY(hipSetDevice(ds.device));
         HIP_TRY(hipStreamSynchronize(ds.s()));
         const int rc = ring_check(ds);
         if (rc) return rc;
     }
+    return ZC_OK;
+}
+
+// Another thread may switch a slot's stream meanwhile (zc_ctx_set_stream_dev), so the handles are read under the lock.  The
+// wait itself runs outside it: launches of other threads go on, and whatever was enqueued on a slot before this call -- on
+// the stream it has now or, through the switch event, on an earlier one -- has completed when the wait returns.
+int zc_ctx_synchronize(zc_ctx* ctx)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::vector<std::pair<int, hipStream_t>> streams;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        for (auto& ds : ctx->devs) streams.emplace_back(ds.device, ds.s());
+    }
+    for (auto& [device, stream] : streams) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    for (auto& ds : ctx->devs)
+        if (const int rc = ring_check(ds)) return rc;
     return ZC_OK;
 }
 
@@ -2314,7 +2335,7 @@ int zc_comm_destroy(zc_ctx* ctx)
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (ctx->comm) {
-        (void)zc_ctx_synchronize(ctx);
+        (void)drain_slots_locked(ctx);
         RCCL_TRY(g_rccl.CommDestroy(ctx->comm));
         ctx->comm = nullptr;
         ctx->world = 1;

@@ -10,6 +10,8 @@ of the same kind as the first input.  All arithmetic runs in the HIP library.
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import threading
 
 import numpy as np
 
@@ -30,15 +32,30 @@ def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "device")
 
 
+def _one_call(method):
+    """The stream binding (_follow_torch_stream), the allocation of the outputs and the launch of one call are one step under
+    the engine's lock: torch's current stream is thread-local and ctypes drops the GIL, so without it another thread could
+    rebind the slot between this thread's bind and its launch, and the kernel would run on that thread's stream.  The lock is
+    re-entrant (MsmBases goes through the engine's helpers); `self` is the Engine, or an object with one in `.engine`."""
+    @functools.wraps(method)
+    def locked(self, *args, **kwargs):
+        with getattr(self, "engine", self)._launch_lock:
+            return method(self, *args, **kwargs)
+    return locked
+
+
 class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
     """One zc_ctx.  `devices=None` = one slot on torch's current device when torch is loaded and sees a GPU; otherwise
     zc_ctx_create(NULL, 0): the calling thread's current HIP device (whatever hipSetDevice chose), read back from the
     context.  The context reads the library's tuning knobs (ZC_* environment variables)
     once, here.  `lib`: another build of the same ABI (tests: the ZC_TEST_HOOKS build)."""
 
+    _launch_lock = threading.RLock()    # the fallback of an object made without __init__; every engine gets its own below
+
     def __init__(self, devices=None, lib=None):
         self.lib = lib if lib is not None else _lib.load()
         self.ctx = C.c_void_p()
+        self._launch_lock = threading.RLock()   # bind + allocate + launch of one call: see _one_call
         self._pinned_stream = False      # set_stream() was called: keep that stream
         self._last_torch_stream = {}     # device slot -> handle of the torch stream last bound to it
         if not devices:
@@ -67,12 +84,14 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
         except Exception:
             pass
 
+    @_one_call
     def set_stream(self, stream_handle):
         """Launch on the caller's HIP stream (handle 0 = the HIP null stream, which is what
         torch.cuda.current_stream().cuda_stream is by default)."""
         _lib.check(self.lib.zc_ctx_set_stream(self.ctx, C.c_void_p(stream_handle), 1), "zc_ctx_set_stream", self.lib)
         self._pinned_stream = True
 
+    @_one_call
     def use_own_stream(self):
         """Back to the default: host batches run on the context's own stream; calls on torch CUDA
         tensors follow torch's current stream of that device (see _follow_torch_stream)."""
@@ -147,6 +166,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
     def _call(self, name, *args):
         _lib.check(getattr(self.lib, name)(self.ctx, *args), name, self.lib)
 
+    @_one_call
     def _rows(self, name, ins, outs, mid=(), tail=(), out=None):
         """One batched entry point, name(ctx, inputs..., mid..., outputs..., n, tail...): `ins` = (array, width, dtype) per
         input, `outs` = (width, dtype) per output, allocated like the first input -- except the first when the caller
@@ -227,6 +247,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
     def _same_kind(self, who, *arrays):
         assert all(_is_torch(x) == _is_torch(arrays[0]) for x in arrays), who + ": the arrays must all be numpy arrays or all torch tensors"
 
+    @_one_call
     def ed_lincomb(self, points, scalars):
         """out[i] = sum_j scalars[i, j] * points[i, j] (zc_ed_lincomb): (n, t, 20) points and (n, t, 5) scalars, t = 1..8 --
         numpy arrays, or contiguous torch tensors on one device (the call then runs on torch's current stream and the result
@@ -253,6 +274,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
     def ris_roundtrip_mul(self, b, k, out=None):
         return self._rows("zc_ris_roundtrip_mul", [(b, 32, U8), (k, 5, U64)], [(32, U8), (0, U8)], out=out)
 
+    @_one_call
     def ris_lincomb(self, enc, scalars, base_scalars=None):
         """out32[i] = compress(base_scalars[i] * B + sum_j scalars[i, j] * decompress(enc[i, j])) (zc_ris_lincomb): (n, t, 32)
         uint8 encodings, (n, t, 5) scalars and, for the basepoint term, (n, 5) base scalars, t + (base term) <= 8 -- numpy
@@ -309,6 +331,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
     def ris_mul_base_compress(self, k): return self._rows("zc_ris_mul_base_compress", [(k, 5, U64)], [(32, U8)])
 
     # ------------------------------------------------------------------ MSM (not in the reference)
+    @_one_call
     def _msm(self, name, points, scalars, out_ptr):
         _, (pp, pk), (n,) = self._inputs([(points, 20, U64), (scalars, 5, U64)])
         self._call(name, pp, pk, n, out_ptr)
@@ -330,6 +353,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
         return {"window_bits": v[0], "windows": v[1], "record_stride": v[2], "run": v[3], "segment_buckets": v[4],
                 "sort_passes": v[5], "table_mib": v[6], "window_groups": v[7]}
 
+    @_one_call
     def msm_batch(self, points, scalars):
         """`batch` independent MSMs (zc_msm_batch): (batch, n, 20) points and (batch, n, 5) scalars -- numpy, or torch tensors
         on one device of this context -- give a (batch, 20) numpy array, row b = sum_i scalars[b, i] * points[b, i]."""
@@ -346,6 +370,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
                 "run": v[4], "segment_buckets": v[5], "sort_passes": v[6], "record_stride": v[7]}
 
     # ---- the exchange step of a sharded MSM (BASELINE configs[4])
+    @_one_call
     def msm_partial(self, points, scalars, out=None):
         """This device's sum left in device memory: a (1, 20) int64 torch CUDA tensor (asynchronous)."""
         import torch
@@ -356,6 +381,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
         self._msm("zc_msm_partial", points, scalars, out.data_ptr())
         return out
 
+    @_one_call
     def ed_fold_ordered(self, parts):
         """((p_0 + p_1) + p_2) + ... in index order, one kernel launch; (count, 20) -> (1, 20)."""
         parts, pp, (n,) = self._prep(parts, 20, U64)
@@ -391,6 +417,7 @@ class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
         self._msm("zc_msm_sharded", points, scalars, out.ctypes.data)
         return out
 
+    @_one_call
     def set_stream_dev(self, slot, stream_handle):
         self._call("zc_ctx_set_stream_dev", slot, C.c_void_p(stream_handle), 1)
         self._pinned_stream = True
@@ -412,6 +439,11 @@ class MsmBases:
     def __init__(self, engine, points, window_bits=0):
         self.engine = engine
         self.id = 0
+        self._create(points, window_bits)
+
+    @_one_call
+    def _create(self, points, window_bits):
+        engine = self.engine
         points, pp, (n,) = engine._prep(points, 20, U64)
         self.n = n
         self.plan = engine.msm_fixed_plan(n, window_bits)
@@ -419,6 +451,7 @@ class MsmBases:
         engine._call("zc_msm_bases_create", pp, n, int(window_bits), C.byref(out))
         self.id = out.value
 
+    @_one_call
     def msm(self, scalars):
         if self.id == 0:
             raise _lib.ZerocafHipError("MsmBases: the table was closed")

@@ -23,6 +23,10 @@ class HashMixin:
         assert 1 <= len(parts) <= MAX_PARTS, "%s: 1..%d parts, got %d" % (name, MAX_PARTS, len(parts))
         assert len(prefix) <= MAX_PREFIX, "%s: a prefix of at most %d bytes" % (name, MAX_PREFIX)
         self._same_kind(name, *parts)
+        with self._launch_lock:                 # bind, allocate and launch as one step (engine._one_call)
+            return self._hash_rows_locked(name, parts, prefix, width, dtype)
+
+    def _hash_rows_locked(self, name, parts, prefix, width, dtype):
         arrs, ptrs, lens, n = [], [], [], None
         for x in parts:
             assert len(x.shape) == 2 and x.shape[1] >= 1, "%s: every part is (n, len) with len >= 1, got %s" % (name, tuple(x.shape))

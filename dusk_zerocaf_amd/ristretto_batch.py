@@ -27,6 +27,10 @@ class RistrettoBatchMixin:
         undecodable term has ok = 0 and is left out of both.  A batch verifies when every ok is 1 and the bytes are zero."""
         given = [x for x in (base_scalars, weights) if x is not None]
         self._same_kind("ris_lincomb_sum", enc, scalars, *given)
+        with self._launch_lock:                 # bind, allocate and launch as one step (engine._one_call)
+            return self._ris_lincomb_sum_locked(enc, scalars, base_scalars, weights)
+
+    def _ris_lincomb_sum_locked(self, enc, scalars, base_scalars, weights):
         (enc, _), (pe, pk), (n, t) = self._inputs([(enc, 32, U8), (scalars, 5, U64)], lead=2)
         per_row = []
         for x in (base_scalars, weights):

@@ -1681,6 +1681,44 @@ def test_concurrent_callers_share_a_context(eng, oracle):
         assert eq(got[name], want[name]), name
 
 
+def test_concurrent_callers_of_the_msm_family_share_a_context(eng, oracle):
+    """The same promise for the entry points that share the slot's MSM workspace (`msm`, `ris_sum`, the side streams `aux` and
+    `grp`) and the staging areas: numpy callers of the bucket MSM, zc_msm_batch, zc_msm_fixed, zc_ris_lincomb_sum and
+    zc_sc_from_sha512 on one context from four threads (the fourth alternates the last two).  Every one of these calls
+    synchronises before it returns; the context's mutex is what keeps them apart."""
+    import threading
+    from tests import async_cases as AC
+    ids = ("msm_partial", "msm_batch_64x33", "msm_fixed", "ris_sum_buckets", "sc_from_sha512")
+    ins = {i: AC.CALLS[i].gen(oracle, 3) for i in ids}
+    table = eng.msm_bases(ins["msm_fixed"][0])
+    runs = {"msm_partial": lambda a: (eng.msm(a[0], a[1]),), "msm_batch_64x33": lambda a: (eng.msm_batch(a[0], a[1]),),
+            "msm_fixed": lambda a: (table.msm(a[1]),), "ris_sum_buckets": lambda a: eng.ris_lincomb_sum(a[0], a[1]),
+            "sc_from_sha512": lambda a: (eng.sc_from_sha512(list(a), prefix=b"async"),)}
+    got, errs = {}, []
+
+    def run(names, reps):
+        try:
+            for _ in range(reps):
+                for name in names:
+                    got[name] = runs[name](ins[name])
+        except Exception as e:                                     # noqa: BLE001
+            errs.append((names, e))
+
+    ts = [threading.Thread(target=run, args=(("msm_partial",), 4)), threading.Thread(target=run, args=(("msm_batch_64x33",), 4)),
+          threading.Thread(target=run, args=(("msm_fixed",), 6)), threading.Thread(target=run, args=(("ris_sum_buckets", "sc_from_sha512"), 3))]
+    try:
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    finally:
+        table.close()
+    assert not errs, errs
+    for name in ids:
+        outs = tuple(np.frombuffer(o, dtype=np.uint8) if isinstance(o, bytes) else o for o in got[name])
+        AC.CALLS[name].check(oracle, ins[name], outs)
+
+
 def test_msm_exchange_inside_the_library(eng, oracle):
     """SURVEY 8e / BASELINE configs[4]: partial sums stay in HBM, are gathered on the device (peer
     copies inside one process, ncclAllGather between processes) and folded in rank order by ONE

@@ -214,6 +214,8 @@ def load_test_hooks() -> C.CDLL:
         _test_lib.zc_test_odd_table.restype = C.c_int
         _test_lib.zc_test_staged_launches.argtypes = [_ctx]
         _test_lib.zc_test_staged_launches.restype = C.c_longlong
+        _test_lib.zc_test_launch_forms.argtypes = [_ctx, C.POINTER(C.c_uint64), C.c_int]
+        _test_lib.zc_test_launch_forms.restype = C.c_int
     return _test_lib
 
 

@@ -4,6 +4,7 @@
 #pragma once
 #include "zc_curve.hip.h"
 #include "zc_msm_plan.h"      // ZC_BLOCK and the constants the MSM kernels share with the host-side plans
+#include "zc_launch_plan.h"   // the RING_* geometry and ZC_COST_BINS, shared with the host's launch choices
 
 namespace zc {
 
@@ -708,7 +709,7 @@ ZC_KERNEL void k_ed_neg(const u64* p, u64* out, size_t n)
 // a counting sort (cost < 1024 bins) and wave w processes the elements idx[64w .. 64w+63], which
 // then have (nearly) equal cost.  Results are scattered back through the same index, so the
 // output order is unchanged.  Three tiny kernels (~tens of microseconds at 2^20).
-constexpr int ZC_COST_BINS = 1024;
+// (ZC_COST_BINS: zc_launch_plan.h, with the layout of the balance workspace)
 
 ZC_DI u32 scalar_cost(const u64 (&l)[5])
 {
@@ -996,14 +997,7 @@ ZC_KERNEL void k_ed_scalar_mul_small(const u64* p, const u64* k, size_t k_stride
 // 14 % SLOWER: co-resident waves then start together, stay in lock step and stall on their table
 // loads together; short-lived workgroups drift apart and cover each other.  The ring keeps the
 // short-lived workgroups.)
-constexpr u32 RING_XCDS = 8;                      // HW_REG_XCC_ID is masked to this range
-constexpr u32 RING_SLOTS = 512;                   // wave slots per XCD
-constexpr u32 RING_TICKET_STRIDE = 32;            // one 128-byte line per XCD's ticket counter
-constexpr u32 RING_STATE_WORDS = RING_XCDS * RING_TICKET_STRIDE + RING_XCDS * RING_SLOTS;   // zeroed per launch
-constexpr u32 RING_ERR_WORD = RING_STATE_WORDS;    // behind them (two words, written once by the host): device address of the error word
-constexpr u32 RING_ALLOC_WORDS = RING_STATE_WORDS + 32;
-constexpr u32 RING_SLOT_DEAD = 0xFFFFFFFFu;       // flag word of a slot whose queue gave up (a generation count never gets there: < 2^19)
-constexpr size_t RING_TABLE_BYTES = (size_t)RING_XCDS * RING_SLOTS * 64 * 1024;
+// (RING_XCDS, RING_SLOTS and the other RING_* geometry constants: zc_launch_plan.h, shared with the host's ring_plan)
 
 // The lane's number, computed afresh wherever it is asked for: `volatile` keeps the compiler from sharing
 // one v_mbcnt result between distant uses, which would pin a vector register across the whole kernel

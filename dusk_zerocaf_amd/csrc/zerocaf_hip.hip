@@ -232,7 +232,7 @@ struct DevState {
     Stream grp;                         // MSM window groups: the chains of the groups above the lowest one, one after the other (highest priority)
     Event ev_grp_go[3], ev_grp_done[3];   // group g's bucket sums are enqueued / its chain is through
 #ifdef ZC_TEST_HOOKS
-    unsigned long long staged_launches = 0;   // element-wise / point launches that took the LDS-staged kernel (zc_test_staged_launches)
+    unsigned long long forms[zc::LAUNCH_FORMS] = {};   // launches per kernel form the plan chose (count_form; zc_test_launch_forms)
 #endif
 
     DevState() = default;
@@ -365,32 +365,17 @@ inline int owner_of(zc_ctx* ctx, std::initializer_list<const void*> ptrs, const 
     return owner_of(ctx, ptrs.begin(), ptrs.size(), who, owner);
 }
 
-inline unsigned grid_for(size_t n) { return (unsigned)((n + zc::ZC_BLOCK - 1) / zc::ZC_BLOCK); }
-
-// Host batches of the long-running kernels (scalar multiplications: >= 10 ms per 2^20 elements)
-// move through the device in chunks so that only the first upload and the last download are
-// exposed. A chunk is a whole number of full-chip rounds of workgroups (2^17 lanes = 512 blocks),
-// otherwise every chunk pays a partially filled tail round: measured on 2^20 strict
-// scalar-muls, 4 x 2^18 takes 26.1 ms, 3 chunks 30.2 ms, 1 chunk 32.0 ms (kernel alone 22.5 ms).
-// Copy-bound calls (field / point element-wise ops) stay in one piece: pageable copies block the
-// calling thread, so chunking them buys no overlap. ZC_HOST_CHUNKS=k forces k chunks.
-constexpr size_t CHUNK_ROUND = (size_t)1 << 17;
-constexpr size_t MAX_CHUNKS = 4096;
-inline size_t host_chunk_elems(size_t cnt, bool heavy, long forced)
+// Every choice between kernel forms, grids and chunk sizes below is asked of zc_launch_plan.h (the MSM pipelines: zc_msm_plan.h);
+// this file launches what it is told.  The test build counts each answer where it is consumed (zc_test_launch_forms).
+using zc::grid_for;
+inline void count_form(DevState& D, zc::LaunchForm form)
 {
-    size_t chunk = cnt;
-    if (forced > 0)
-        chunk = (cnt + forced - 1) / forced;
-    else if (heavy && cnt >= 4 * CHUNK_ROUND)
-        // eight chunks, but none below 2^18 elements: the exposed ends (first upload, last download) shrink with
-        // the chunk, the per-chunk launches lose efficiency below 2^18 (2^22 strict scalar-muls: 16 chunks of
-        // 2^18 89.4 ms, 8 of 2^19 83.1 ms, 4 of 2^20 85.7 ms; 2^20: 4 chunks of 2^18 23.8 ms, 8 of 2^17 34.8 ms)
-        chunk = std::max(2 * CHUNK_ROUND, (cnt / 8 + CHUNK_ROUND - 1) / CHUNK_ROUND * CHUNK_ROUND);
-    else if (heavy && cnt >= 2 * CHUNK_ROUND)
-        chunk = CHUNK_ROUND;
-    chunk = (chunk + 1023) / 1024 * 1024;
-    return std::max(chunk, (cnt + MAX_CHUNKS - 1) / MAX_CHUNKS);
+#ifdef ZC_TEST_HOOKS
+    D.forms[form]++;
+#endif
+    (void)D, (void)form;
 }
+
 // Launch functor: receives device pointers in argument order, element count, device state; returns a status.  A launch that
 // fails ends its device job: no further chunk is started, the job's streams are drained and the status (with the message, also
 // from a worker thread) goes to the caller; the outputs are then unspecified.
@@ -438,7 +423,7 @@ int run_batched(zc_ctx* ctx, const Arg* args, int nargs, size_t n, Launch&& laun
         const size_t lo = di * per, hi = std::min(n, lo + per);
         if (lo >= hi) return ZC_OK;
         const size_t total = hi - lo;
-        const size_t chunk = host_chunk_elems(total, heavy, ctx->devs[di].tune.host_chunks);
+        const size_t chunk = zc::host_chunk_elems(total, heavy, ctx->devs[di].tune.host_chunks);
         const size_t nchunks = (total + chunk - 1) / chunk;
         DevState& ds = ctx->devs[di];
         long calls = 0;
@@ -572,118 +557,60 @@ typedef void (*kun_t)(const u64*, u64*, size_t);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Streams larger than this (bytes over all arrays of the call) use the LDS-staged kernel
-// when one is given: it wins only for the compute-free two-input ops beyond the
-// 256 MB Infinity Cache (zc_kernels.hip.h, "LDS-staged element I/O").
-constexpr size_t STREAM_BYTES = (size_t)256 << 20;
-
-// The LDS-staged form of an element-wise kernel, taken when the call's arrays are all 16-byte aligned and hold more than
-// `min_bytes` together: STREAM_BYTES for the 40-byte element ops; the point ops -- 160-byte records, far beyond what a lane
-// reads well on its own -- from the first full launch on, with a workgroup size of their own.
+// The LDS-staged form of an element-wise kernel and the rule that says when it is taken (zc_launch_plan.h: StagedRule); the
+// default rule is the 40-byte element ops': more than STREAM_BYTES over the call's arrays.
 template <class K>
 struct Staged {
     K kernel = nullptr;                  // null: the op has no staged form
-    size_t min_bytes = STREAM_BYTES;
-    unsigned block = zc::ZC_BLOCK;
+    zc::StagedRule rule;
 };
-// The test build can lower STREAM_BYTES itself (ZC_TEST_STREAM_MIN_BYTES) so that small batches reach the ops staged from there on.
-inline size_t staged_min(const DevState& D, size_t min_bytes)
+// The point ops: staged above ED_STAGED_MIN_POINTS rows, with a workgroup size of their own.
+template <class K>
+Staged<K> staged_points(K k) { return {k, {0, zc::ED_STAGED_MIN_POINTS, zc::ED_STAGED_BLOCK}}; }
+// One launch over the arrays p... (inputs, then the output) of cnt rows of `per` limbs: the staged or the per-lane kernel
+template <class K, class... P>
+int launch_elementwise(DevState& D, size_t cnt, size_t per, K k, const Staged<K>& st, P... p)
 {
-#ifdef ZC_TEST_HOOKS
-    if (min_bytes == STREAM_BYTES && D.tune.test_stream_min > 0) return (size_t)D.tune.test_stream_min;
-#endif
-    (void)D;
-    return min_bytes;
-}
-// (the test build counts the launches that took a staged kernel: zc_test_staged_launches)
-inline void count_staged(DevState& D, bool staged)
-{
-#ifdef ZC_TEST_HOOKS
-    D.staged_launches += staged ? 1 : 0;
-#endif
-    (void)D, (void)staged;
+    const zc::ElementwiseForm f = zc::elementwise_form(cnt, per, sizeof...(p), st.kernel != nullptr, st.rule, D.tune.test_stream_min, (aligned16(p) && ...));
+    count_form(D, f.form);
+    hipLaunchKernelGGL(f.form == zc::FORM_STAGED ? st.kernel : k, dim3((unsigned)((cnt + f.block - 1) / f.block)), dim3(f.block), 0, D.s(), p..., cnt);
+    return ZC_OK;
 }
 // out = a op b / out = op a over rows of `per` limbs
 int binop(zc_ctx* ctx, kbin_t k, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, size_t per, Staged<kbin_t> st = {})
 {
-    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, const u64* db, u64* dout) {
-        const bool staged = st.kernel && cnt * sizeof(u64) * per * 3 > staged_min(D, st.min_bytes) && aligned16(da) && aligned16(db) && aligned16(dout);
-        const unsigned blk = staged ? st.block : (unsigned)zc::ZC_BLOCK;
-        count_staged(D, staged);
-        hipLaunchKernelGGL(staged ? st.kernel : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), da, db, dout, cnt);
-        return ZC_OK;
-    }, ROWS(a, per), ROWS(b, per), ROWS(out, per));
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, const u64* db, u64* dout) { return launch_elementwise(D, cnt, per, k, st, da, db, dout); },
+                   ROWS(a, per), ROWS(b, per), ROWS(out, per));
 }
 int unop(zc_ctx* ctx, kun_t k, const uint64_t* a, uint64_t* out, size_t n, size_t per, Staged<kun_t> st = {})
 {
-    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) {
-        const bool staged = st.kernel && cnt * sizeof(u64) * per * 2 > staged_min(D, st.min_bytes) && aligned16(da) && aligned16(dout);
-        const unsigned blk = staged ? st.block : (unsigned)zc::ZC_BLOCK;
-        count_staged(D, staged);
-        hipLaunchKernelGGL(staged ? st.kernel : k, dim3((unsigned)((cnt + blk - 1) / blk)), dim3(blk), 0, D.s(), da, dout, cnt);
-        return ZC_OK;
-    }, ROWS(a, per), ROWS(out, per));
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) { return launch_elementwise(D, cnt, per, k, st, da, dout); },
+                   ROWS(a, per), ROWS(out, per));
 }
 
-// Cost-sorted permutation for the unified-step kernels (see zc_kernels.hip.h "lane balancing").
-// Returns nullptr (natural order) for small batches or when scratch cannot be had.
-// The persistent-wave kernel walks it; the block-shaped kernels (small batches, ZC_SCHED=block) rank their 256 scalars in
-// LDS instead, which keeps HBM traffic algorithmic.
-constexpr size_t BALANCE_MIN_N = 1 << 14;
-constexpr size_t BAL_COUNTERS = 64;                       // u32 work counters of the persistent kernels, after the bins
+// The cost-sorted permutation of a strict batch that asks for one (zc_launch_plan.h: strict_wants_permutation), in the balance
+// workspace: bins, counters, then the indices.  Returns nullptr (natural order) when scratch cannot be had.
 const zc::u32* balance_index(DevState& D, const u64* k, size_t cnt, zc::u32** counter)
 {
-    if (cnt < BALANCE_MIN_N || cnt > 0xFFFFFFFFull) return nullptr;
-    const size_t need = (zc::ZC_COST_BINS + BAL_COUNTERS + cnt) * sizeof(zc::u32);
-    if (D.bal.grow(need) != ZC_OK) return nullptr;
+    if (D.bal.grow(zc::balance_bytes(cnt)) != ZC_OK) return nullptr;
     zc::u32* hist = D.bal.as<zc::u32>();
-    zc::u32* idx = hist + zc::ZC_COST_BINS + BAL_COUNTERS;
-    if (hipMemsetAsync(hist, 0, (zc::ZC_COST_BINS + BAL_COUNTERS) * sizeof(zc::u32), D.s()) != hipSuccess) return nullptr;
+    zc::u32* idx = hist + zc::ZC_COST_BINS + zc::BAL_COUNTERS;
+    if (hipMemsetAsync(hist, 0, (zc::ZC_COST_BINS + zc::BAL_COUNTERS) * sizeof(zc::u32), D.s()) != hipSuccess) return nullptr;
     hipLaunchKernelGGL(zc::k_sm_cost_hist, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), k, hist, cnt);
     hipLaunchKernelGGL(zc::k_sm_cost_scan, dim3(1), dim3(zc::ZC_BLOCK), 0, D.s(), hist);
     hipLaunchKernelGGL(zc::k_sm_cost_scatter, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), k, hist, idx, cnt);
-    if (counter) *counter = hist + zc::ZC_COST_BINS;
+    *counter = hist + zc::ZC_COST_BINS;
     return idx;
 }
-// Strict scalar-mul batches from this size on run on persistent waves over the cost-sorted
-// permutation (k_ed_scalar_mul_pw: generic steps alternating with wave-uniform doubling steps); ZC_SCHED=unified keeps the
-// persistent waves on generic steps only, ZC_SCHED=block keeps one workgroup per 256 elements.
-constexpr size_t PW_MIN_ELEMS = (size_t)1 << 17;
-
-// Launches of at most one workgroup per CU keep a single wave on every SIMD; a lone wave cannot
-// hide the latency of the column-ordered multiplier's serial chain, so those launches run the
-// variant with independent column chains (2^16 units: 2.09 -> 1.79 ms; from 384 workgroups on the
-// default kernel is faster again).
-constexpr unsigned SMALL_LAUNCH_BLOCKS = 256;
-constexpr size_t QUAD_LAUNCH_ELEMS = (size_t)1 << 14;     // 4 lanes per element still leave one wave per SIMD
-typedef void (*strict_kernel_t)(const u64*, const u64*, size_t, u64*, size_t);
-inline strict_kernel_t strict_kernel_for(size_t cnt)
-{
-    return grid_for(cnt) <= SMALL_LAUNCH_BLOCKS ? zc::k_ed_scalar_mul_small : zc::k_ed_scalar_mul;
-}
-// The windowed-core kernels keep 1 KB of table scratch per lane in a ring of wave slots per XCD
-// (zc_kernels.hip.h: ring_acquire / ring_release): 256 MB of tables plus 17 KB of tickets and flags, zeroed
-// on the stream before every launch.  One launch covers the batch (the kernels index with 32 bits:
-// beyond 2^31 elements the batch goes in pieces, one after the other on the stream).
-// launch(table, ring_state, slots_per_xcd, offset, count).  ZC_RING_SLOTS=k (1..512) shrinks the ring so that
-// waves really wait for one another (tests; the default leaves more slots than waves fit an XCD).
-// zc_ed_lincomb takes `slot_units` consecutive 64 KB units per wave slot, one per term (zc_kernels.hip.h: k_ed_lincomb).
-// The table area then grows with the slot, up to LINCOMB_MAX_UNITS units per XCD (1 GB in all): 512 slots up to four terms,
-// then 409, 341, 292, 256 for five to eight.  Waves of that kernel resident per XCD: 384 up to five terms, then 320, 320,
-// 256 (LDS-bound) -- so the ring has a free slot for every resident wave except at seven terms, where up to 28 waves per
-// XCD queue for one (by the ring's own protocol).  The single-unit kernels address the first 256 MB of the area whatever
-// its size (their XCD stride stays RING_SLOTS units).
-constexpr size_t FAST_MAX_LAUNCH = (size_t)1 << 31;
-constexpr size_t LINCOMB_MAX_UNITS = 2048;
-inline size_t ring_units_per_xcd(size_t slot_units)
-{
-    return slot_units <= 1 ? (size_t)zc::RING_SLOTS : std::min((size_t)zc::RING_SLOTS * slot_units, LINCOMB_MAX_UNITS);
-}
+// The windowed-core kernels' table ring (zc_launch_plan.h: ring_plan; zc_kernels.hip.h: ring_acquire / ring_release): the table
+// area and the ring state are allocated on first use, tickets and flags zeroed on the stream before every launch, the batch
+// cut into launches of at most max_launch rows.  launch(table, ring_state, slots_per_xcd, offset, count).
+// `slot_units`: consecutive 64 KB units per wave slot (the lincombs: one per term).
 template <class L>
 int fast_ring(DevState& D, size_t cnt, L&& launch, size_t slot_units = 1)
 {
-    const size_t units_per_xcd = ring_units_per_xcd(slot_units);
-    if (int rc = D.fast.grow(zc::RING_TABLE_BYTES / zc::RING_SLOTS * units_per_xcd)) return rc;
+    const zc::RingPlan ring = zc::ring_plan(slot_units, D.tune.ring_slots);
+    if (int rc = D.fast.grow(ring.table_bytes)) return rc;
     if (!D.ring) {
         // The error word lives in pinned HOST memory the device can write (a wave that gives up stores through the
         // address parked behind the ring state): the host reads it at every entry point without any synchronisation.
@@ -706,16 +633,13 @@ int fast_ring(DevState& D, size_t cnt, L&& launch, size_t slot_units = 1)
             return fail(ZC_ERR_HIP, "windowed core: ring state setup", e);
         }
     }
-    // a launch hands out fewer than 2^19 generations of its slots (the 19-bit field of the word ring_acquire parks)
-    const zc::u32 slots = std::min(D.tune.ring_slots ? (zc::u32)D.tune.ring_slots : zc::RING_SLOTS, (zc::u32)(units_per_xcd / slot_units));
-    zc::u32 slots_arg = slots;
+    zc::u32 slots_arg = ring.slots;
 #ifdef ZC_TEST_HOOKS
     slots_arg |= (zc::u32)D.tune.test_ring_spins << 16;      // test build: the kernels take their spin limit from the upper half
 #endif
-    const size_t max_launch = std::min(FAST_MAX_LAUNCH, (size_t)slots << 24);
-    for (size_t off = 0; off < cnt; off += max_launch) {
+    for (size_t off = 0; off < cnt; off += ring.max_launch) {
         HIP_TRY(hipMemsetAsync(D.ring.as<void>(), 0, zc::RING_STATE_WORDS * sizeof(zc::u32), D.s()));
-        launch(D.fast.as<zc::u32>(), D.ring.as<zc::u32>(), slots_arg, off, std::min(max_launch, cnt - off));
+        launch(D.fast.as<zc::u32>(), D.ring.as<zc::u32>(), slots_arg, off, std::min(ring.max_launch, cnt - off));
     }
 #ifdef ZC_TEST_HOOKS
     if (D.tune.test_ring_poison) *D.ring_error() = 1;            // pretend a wave gave up (exercises the report-and-recover path)
@@ -734,22 +658,26 @@ int ring_check(DevState& D)
     return fail(ZC_ERR_HIP, "windowed core: a wave timed out waiting for its table slot; the rows it owned hold poison (all ones) -- "
                             "the outputs of the last windowed-core calls on this device are not valid");
 }
-// cnt strict scalar multiplications of device arrays on D.s(): the kernel choice of zc_ed_scalar_mul
-void scalar_mul_on_device(DevState& D, const u64* p, const u64* k, u64* out, size_t cnt)
+// cnt strict scalar multiplications of device arrays on D.s(), in the form zc_launch_plan.h names (strict_form): the one
+// place a strict launch is made.  quad_ok: zc_ed_scalar_mul's own choice; false keeps one lane per row (a small zc_msm shard).
+void scalar_mul_on_device(DevState& D, const u64* p, const u64* k, u64* out, size_t cnt, bool quad_ok = true)
 {
-    if (cnt >= PW_MIN_ELEMS && !D.tune.sched_block) {
-        zc::u32* counter = nullptr;
-        if (const zc::u32* perm = balance_index(D, k, cnt, &counter)) {
-            hipLaunchKernelGGL(D.tune.sched_unified ? zc::k_ed_scalar_mul_pw_unified : zc::k_ed_scalar_mul_pw, dim3((unsigned)(3 * D.cus)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, perm, counter, (zc::u32)cnt);
-            return;
-        }
-    }
-    if (cnt <= QUAD_LAUNCH_ELEMS) {
-        // four lanes per element: the batch cannot fill the chip anyway, so buy latency with lanes
-        hipLaunchKernelGGL(zc::k_ed_scalar_mul_quad, dim3((unsigned)((cnt + 63) / 64)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, cnt);
+    zc::u32* counter = nullptr;
+    const zc::u32* perm = zc::strict_wants_permutation(cnt, D.tune.sched_block) ? balance_index(D, k, cnt, &counter) : nullptr;
+    const zc::StrictPlan sp = zc::strict_form(cnt, D.tune.sched_unified, perm != nullptr, D.cus, quad_ok);
+    count_form(D, sp.form);
+    switch (sp.form) {
+    case zc::FORM_STRICT_PW:
+    case zc::FORM_STRICT_PW_UNIFIED:
+        hipLaunchKernelGGL(sp.form == zc::FORM_STRICT_PW_UNIFIED ? zc::k_ed_scalar_mul_pw_unified : zc::k_ed_scalar_mul_pw, dim3(sp.grid), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out,
+                           perm, counter, (zc::u32)cnt);
         return;
+    case zc::FORM_STRICT_QUAD:
+        hipLaunchKernelGGL(zc::k_ed_scalar_mul_quad, dim3(sp.grid), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, out, cnt);
+        return;
+    default:
+        hipLaunchKernelGGL(sp.form == zc::FORM_STRICT_SMALL ? zc::k_ed_scalar_mul_small : zc::k_ed_scalar_mul, dim3(sp.grid), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, (size_t)5, out, cnt);
     }
-    hipLaunchKernelGGL(strict_kernel_for(cnt), dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), p, k, (size_t)5, out, cnt);
 }
 int scalar_mul_impl(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t* out, size_t n)
 {
@@ -1020,7 +948,7 @@ int msm_on_device(DevState& D, const u64* dP, const u64* dK, size_t cnt, const u
         if (int rc = D.msm.grow(prod_bytes + ((cnt + 1) / 2) * 160 + 256)) return rc;
         u64* const prod = D.msm.as<u64>();
         u64* const half = (u64*)(D.msm.as<char>() + prod_bytes);
-        hipLaunchKernelGGL(strict_kernel_for(cnt), dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dP, dK, (size_t)5, prod, cnt);
+        scalar_mul_on_device(D, dP, dK, prod, cnt, false);
         *result = fold_all(D, prod, half, cnt);
         HIP_TRY(hipGetLastError());
         return ZC_OK;
@@ -1252,29 +1180,18 @@ int msm_batch_on_device(DevState& D, const u64* dP, const u64* dK, size_t n, siz
     return ZC_OK;
 }
 
-// Montgomery's trick shares one inversion among the c consecutive elements of a lane (3 multiplications per
-// element + one inversion per lane).  c = cnt / INV_LANES_TARGET keeps that many lanes busy, capped at 64;
-// below 2 the kernels take one element per lane.  ZC_INV_CHUNK=c overrides (tuning, tests).
-constexpr size_t INV_LANES_TARGET = 65536;
-inline size_t inv_chunk(size_t cnt, const Tuning& tune)
-{
-    if (tune.inv_chunk) return (size_t)tune.inv_chunk;
-    size_t c = cnt / INV_LANES_TARGET;
-    return c > 32 ? 32 : c;
-}
-// The launch of an op with one inversion per element over the buffers p...: `k` (one element per lane) for a tiny batch or when
-// the output aliases an input, otherwise the chunked kernel -- `k_lone`, the independent-chain multiplier, when the lanes leave
-// at most one wave per SIMD (2^20 elements: BASELINE configs[1], -7 %).
+// The launch of an op with one inversion per element over the buffers p... in the form zc_launch_plan.h names (inversion_form):
+// `k` with one element per lane, or the chunked kernel on lanes that share an inversion among c elements -- `k_lone` its
+// independent-chain multiplier form.
 template <class K, class KC, class... P>
 int launch_shared_inversions(DevState& D, size_t cnt, bool in_place, K k, KC k_chunked, KC k_lone, P... p)
 {
-    const size_t c = inv_chunk(cnt, D.tune);
-    if (c < 2 || in_place) {
-        hipLaunchKernelGGL(k, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt);
-    } else {
-        const size_t lanes = (cnt + c - 1) / c;
-        hipLaunchKernelGGL(lanes <= (size_t)D.cus * 256 ? k_lone : k_chunked, dim3(grid_for(lanes)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt, (int)c);
-    }
+    const zc::InversionPlan ip = zc::inversion_form(cnt, in_place, D.tune.inv_chunk, D.cus);
+    count_form(D, ip.form);
+    if (ip.form == zc::FORM_INV_PER_ELEMENT)
+        hipLaunchKernelGGL(k, dim3(grid_for(ip.lanes)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt);
+    else
+        hipLaunchKernelGGL(ip.form == zc::FORM_INV_LONE ? k_lone : k_chunked, dim3(grid_for(ip.lanes)), dim3(zc::ZC_BLOCK), 0, D.s(), p..., cnt, (int)ip.c);
     return ZC_OK;
 }
 
@@ -1319,15 +1236,12 @@ int hash_rows_call(zc_ctx* ctx, void (*k)(const zc::HashMsg, T*, size_t), const 
     args[nparts] = Arg{out, sizeof(T) * out_per, true};
     return run_batched(ctx, args, (int)nparts + 1, n, [&](void** d, size_t cnt, DevState& D) -> int {
         zc::HashMsg piece = m;
-        bool words = prefix_len % 8 == 0;
+        unsigned mod8[zc::HASH_MAX_PARTS];
         for (size_t j = 0; j < nparts; j++) {
             piece.part[j] = static_cast<const uint8_t*>(d[j]);
-            words = words && part_len[j] % 8 == 0 && reinterpret_cast<uintptr_t>(d[j]) % 8 == 0;
+            mod8[j] = (unsigned)(reinterpret_cast<uintptr_t>(d[j]) % 8);
         }
-#ifdef ZC_TEST_HOOKS
-        if (D.tune.test_hash_bytes) words = false;
-#endif
-        piece.words = words ? 1 : 0;
+        piece.words = zc::hash_reader_words(prefix_len, part_len, mod8, nparts, D.tune.test_hash_bytes) ? 1 : 0;
         hipLaunchKernelGGL(k, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), piece, static_cast<T*>(d[nparts]), cnt);
         return ZC_OK;
     }, false);
@@ -1480,16 +1394,16 @@ int zc_fe_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size
 #define ZC_MULSQ_STAGED 1            // 0: A/B build with per-lane accesses at every size
 #endif
 #ifndef ZC_MULSQ_STAGED_MIN_BYTES
-#define ZC_MULSQ_STAGED_MIN_BYTES STREAM_BYTES
+#define ZC_MULSQ_STAGED_MIN_BYTES zc::STREAM_BYTES
 #endif
 // Neg: one input array, no arithmetic to speak of.  Round 6 A/B at 2^24 / 2^26 decides whether the staged form ships
 // (profiles/r06_experiments/neg_staged_ab.md); a kernel without a launch site is not kept.
 #ifndef ZC_NEG_STAGED
 #define ZC_NEG_STAGED 1
 #endif
-int zc_fe_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_mul, a, b, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_fe_mul_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
+int zc_fe_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_fe_mul, a, b, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_fe_mul_stream : nullptr, {ZC_MULSQ_STAGED_MIN_BYTES}}); }
 int zc_fe_neg(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_neg, a, o, n, 5, {ZC_NEG_STAGED ? zc::k_fe_neg_stream : nullptr}); }
-int zc_fe_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_square, a, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_fe_square_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
+int zc_fe_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_fe_square, a, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_fe_square_stream : nullptr, {ZC_MULSQ_STAGED_MIN_BYTES}}); }
 
 int zc_fe_invert(zc_ctx* ctx, const uint64_t* a, uint64_t* out, uint8_t* ok, size_t n)
 {
@@ -1543,9 +1457,9 @@ int zc_fe_inv_sqrt(zc_ctx* ctx, const uint64_t* a, uint64_t* out, uint8_t* was_s
 // ---- Scalar
 int zc_sc_add(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_add, a, b, o, n, 5, {zc::k_sc_add_stream}); }
 int zc_sc_sub(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_sub, a, b, o, n, 5, {zc::k_sc_sub_stream}); }
-int zc_sc_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_mul, a, b, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_sc_mul_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
+int zc_sc_mul(zc_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) { return binop(c, zc::k_sc_mul, a, b, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_sc_mul_stream : nullptr, {ZC_MULSQ_STAGED_MIN_BYTES}}); }
 int zc_sc_neg(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_neg, a, o, n, 5, {ZC_NEG_STAGED ? zc::k_sc_neg_stream : nullptr}); }
-int zc_sc_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_square, a, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_sc_square_stream : nullptr, ZC_MULSQ_STAGED_MIN_BYTES}); }
+int zc_sc_square(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_square, a, o, n, 5, {ZC_MULSQ_STAGED ? zc::k_sc_square_stream : nullptr, {ZC_MULSQ_STAGED_MIN_BYTES}}); }
 // S-x rows: the Scalar operations beside the default scalar-mul path
 int zc_sc_half(zc_ctx* c, const uint64_t* a, uint64_t* o, size_t n) { return unop(c, zc::k_sc_half, a, o, n, 5); }
 int zc_sc_pow(zc_ctx* c, const uint64_t* a, const uint64_t* e, uint64_t* o, size_t n) { return binop(c, zc::k_sc_pow, a, e, o, n, 5); }
@@ -1583,13 +1497,11 @@ int zc_sc_invert(zc_ctx* ctx, const uint64_t* a, uint64_t* out, uint8_t* ok, siz
 }
 
 // ---- EdwardsPoint
-// staged records from 2^12 points on (below, a launch is a handful of workgroups and the barriers only cost)
-constexpr size_t ED_STAGED_MIN_BYTES = (size_t)160 * 3 << 12;     // binop compares cnt * 160 * 3 against it: above 2^12 points
-constexpr size_t ED_STAGED_MIN_BYTES_1 = (size_t)160 * 2 << 12;   // unop compares cnt * 160 * 2: the same 2^12 points for double / neg
-int zc_ed_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_add, p, q, o, n, 20, {zc::k_ed_add_staged, ED_STAGED_MIN_BYTES, zc::ED_STAGED_BLOCK}); }
-int zc_ed_sub(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_sub, p, q, o, n, 20, {zc::k_ed_sub_staged, ED_STAGED_MIN_BYTES, zc::ED_STAGED_BLOCK}); }
-int zc_ed_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_double, p, o, n, 20, {zc::k_ed_double_staged, ED_STAGED_MIN_BYTES_1, zc::ED_STAGED_BLOCK}); }
-int zc_ed_neg(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_neg, p, o, n, 20, {zc::k_ed_neg_staged, ED_STAGED_MIN_BYTES_1, zc::ED_STAGED_BLOCK}); }
+// staged records above 2^12 points (zc_launch_plan.h: ED_STAGED_MIN_POINTS)
+int zc_ed_add(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_add, p, q, o, n, 20, staged_points(zc::k_ed_add_staged)); }
+int zc_ed_sub(zc_ctx* c, const uint64_t* p, const uint64_t* q, uint64_t* o, size_t n) { return binop(c, zc::k_ed_sub, p, q, o, n, 20, staged_points(zc::k_ed_sub_staged)); }
+int zc_ed_double(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_double, p, o, n, 20, staged_points(zc::k_ed_double_staged)); }
+int zc_ed_neg(zc_ctx* c, const uint64_t* p, uint64_t* o, size_t n) { return unop(c, zc::k_ed_neg, p, o, n, 20, staged_points(zc::k_ed_neg_staged)); }
 
 // the reference's other scalar multiplications, one lane per row: (point, scalar) -> point, a long-running kernel
 static int scalar_mul_variant(zc_ctx* ctx, kbin_t k, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n)
@@ -1617,11 +1529,10 @@ int zc_ed_lincomb(zc_ctx* ctx, const uint64_t* points, const uint64_t* scalars, 
     if (terms < 1 || terms > ZC_LINCOMB_MAX_TERMS) return fail(ZC_ERR_BAD_ARG, "zc_ed_lincomb: terms must be 1..ZC_LINCOMB_MAX_TERMS");
     if (n >= ((size_t)1 << 31) / terms + (((size_t)1 << 31) % terms != 0)) return fail(ZC_ERR_BAD_ARG, "zc_ed_lincomb: n * terms must stay below 2^31");
     return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, const u64* dk, u64* dout) -> int {
-        // five and more terms: 128-lane workgroups keep a workgroup's LDS (36 bytes per lane and term) below 37 KB
-        const unsigned block = terms > 4 ? 128u : (unsigned)zc::ZC_BLOCK;
-        const zc::u32 units = (zc::u32)ring_units_per_xcd(terms);
+        const zc::LincombLaunch ll = zc::lincomb_launch(terms);
+        const zc::u32 units = (zc::u32)zc::ring_units_per_xcd(terms);
         if (int rc = fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
-                hipLaunchKernelGGL(zc::k_ed_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * terms * block, D.s(),
+                hipLaunchKernelGGL(zc::k_ed_lincomb, dim3((unsigned)((c + ll.block - 1) / ll.block)), dim3(ll.block), ll.lds_bytes, D.s(),
                                    dp + 20 * terms * off, dk + 5 * terms * off, (zc::u32)terms, dout + 20 * off, table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
             }, terms))
             return rc;
@@ -1777,11 +1688,10 @@ int zc_ris_lincomb(zc_ctx* ctx, const uint8_t* in32, const uint64_t* scalars, si
         const zc::u32* comb = nullptr;
         if (dbase)
             if (int rc = base_table(D, &comb)) return rc;
-        // as zc_ed_lincomb: 128-lane workgroups from five scalar slots on (36 bytes of LDS per lane and slot)
-        const unsigned block = slots_used > 4 ? 128u : (unsigned)zc::ZC_BLOCK;
-        const zc::u32 units = (zc::u32)ring_units_per_xcd(terms);
+        const zc::LincombLaunch ll = zc::lincomb_launch(slots_used);
+        const zc::u32 units = (zc::u32)zc::ring_units_per_xcd(terms);
         return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
-            hipLaunchKernelGGL(zc::k_ris_lincomb, dim3((unsigned)((c + block - 1) / block)), dim3(block), 36 * slots_used * block, D.s(),
+            hipLaunchKernelGGL(zc::k_ris_lincomb, dim3((unsigned)((c + ll.block - 1) / ll.block)), dim3(ll.block), ll.lds_bytes, D.s(),
                                din + 32 * terms * off, dk + 5 * terms * off, (zc::u32)terms, dbase ? dbase + 5 * off : nullptr, dout + 32 * off,
                                dok ? dok + off : nullptr, comb, table, ring, slots, units, (zc::u32)terms, (zc::u32)c);
         }, terms);
@@ -1949,15 +1859,25 @@ int zc_test_odd_table(zc_ctx* ctx, uint64_t* out_dev_points)
     HIP_TRY(hipStreamSynchronize(D.s()));
     return ZC_OK;
 }
-// Test hook: how many element-wise / point launches of this context took their LDS-staged kernel so far (all device slots).
-// Lets a parity test assert that the staged kernel -- not the per-lane one -- produced the output it compared.
+// Test hook: how many launches of this context took each kernel form so far (all device slots), counted where the answer of
+// zc_launch_plan.h is consumed: counts[f] for the first min(n, LAUNCH_FORMS) enumerators f of zc::LaunchForm.  Lets a test assert
+// that the form it names -- not another one -- produced the output it compared.
+int zc_test_launch_forms(zc_ctx* ctx, uint64_t* counts, int n)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    REQUIRE(counts);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    for (int f = 0; f < n && f < zc::LAUNCH_FORMS; f++) {
+        counts[f] = 0;
+        for (auto& d : ctx->devs) counts[f] += d.forms[f];
+    }
+    return ZC_OK;
+}
+// The same for the LDS-staged form of the element-wise / point kernels alone.
 long long zc_test_staged_launches(zc_ctx* ctx)
 {
-    if (!ctx) return -1;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    unsigned long long t = 0;
-    for (auto& d : ctx->devs) t += d.staged_launches;
-    return (long long)t;
+    uint64_t counts[zc::FORM_STAGED + 1];
+    return zc_test_launch_forms(ctx, counts, zc::FORM_STAGED + 1) == ZC_OK ? (long long)counts[zc::FORM_STAGED] : -1;
 }
 #endif  // ZC_TEST_HOOKS
 

@@ -25,7 +25,7 @@ SAMPLE_STEP = 2053                      # large batches: every 2053rd row and th
 SMALL_ROWS = 300                        # up to here every row does
 FILLER_ROWS = 1 << 15                   # the strict scalar-mul that keeps stream 1 busy for about a millisecond
 CORE_ROWS = 4097                        # the windowed core: 64 full waves and one row
-PW_ROWS = ET.PW_MIN_ELEMS + 77          # persistent waves over the cost-sorted rows (zerocaf_hip.hip PW_MIN_ELEMS)
+PW_ROWS = ET.PW_MIN_ELEMS + 77          # persistent waves over the cost-sorted rows (zc_launch_plan.h PW_MIN_ELEMS)
 BUCKET_N = ET.MSM_BUCKET_MIN_N          # the smallest shard of the bucket pipeline (zc_msm_plan.h MSM_BUCKET_MIN_N)
 GROUPED_ENV = {"ZC_MSM_WINDOW": "8", "ZC_MSM_GROUPS": "20,10,3"}     # 33 windows in three groups: chains of the upper two on `grp`
 INV_ENV = {"ZC_INV_CHUNK": "7"}

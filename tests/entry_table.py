@@ -17,12 +17,13 @@ from tests import vectors as V
 
 U64, U8 = np.dtype(np.uint64), np.dtype(np.uint8)
 
-# ---- launch thresholds, each beside the source line it mirrors (dusk_zerocaf_amd/csrc/zerocaf_hip.hip)
-ED_STAGED_MIN_POINTS = 1 << 12          # ED_STAGED_MIN_BYTES = 160 * 3 << 12: add / sub / double / neg stage their records ABOVE 2^12 points
-QUAD_LAUNCH_ELEMS = 1 << 14             # QUAD_LAUNCH_ELEMS: strict scalar-mul batches up to here take four lanes per row
+# ---- launch thresholds, each beside the rule of dusk_zerocaf_amd/csrc/zc_launch_plan.h it mirrors.  Literals, because this module
+# is imported where nothing is compiled; tests/test_launch_plan_emul.py asks the header for the form on both sides of each.
+ED_STAGED_MIN_POINTS = 1 << 12          # ED_STAGED_MIN_POINTS (elementwise_form): add / sub / double / neg stage their records ABOVE 2^12 points
+QUAD_LAUNCH_ELEMS = 1 << 14             # QUAD_LAUNCH_ELEMS (strict_form): strict scalar-mul batches up to here take four lanes per row
 STRICT_SMALL_MAX_ELEMS = 1 << 16        # strict_kernel_for: grid_for(cnt) <= SMALL_LAUNCH_BLOCKS (256 workgroups of ZC_BLOCK = 256 rows) takes the
                                         # independent-chain kernel k_ed_scalar_mul_small, larger batches one workgroup per 256 rows (k_ed_scalar_mul)
-PW_MIN_ELEMS = 1 << 17                  # PW_MIN_ELEMS: strict batches from here on run on persistent waves over the cost-sorted rows
+PW_MIN_ELEMS = 1 << 17                  # PW_MIN_ELEMS (strict_wants_permutation): strict batches from here on run on persistent waves over the cost-sorted rows
 MSM_BUCKET_MIN_N = 4096                 # zc_msm_plan.h MSM_BUCKET_MIN_N: zc_msm shards from here on take the bucket pipeline
 MSM_BATCH_BUCKET_MIN_N = 64             # zc_msm_plan.h ZC_MSM_BATCH_BUCKET_MIN_N: zc_msm_batch instances below it are scalar-muls + folds
 LINCOMB_MAX_TERMS = 8                   # ZC_LINCOMB_MAX_TERMS (include/zerocaf_hip.h)

@@ -427,6 +427,8 @@ class EmulBackend:
 
 # ------------------------------------------------------------------ the Engine backend (GPU tier)
 STRICT_OPS = ("ed_scalar_mul", "sm_tiles")
+# zc::LaunchForm (dusk_zerocaf_amd/csrc/zc_launch_plan.h) in the header's order; tests/test_launch_plan_emul.py keeps it so
+LAUNCH_FORMS = ("per_lane", "staged", "strict_quad", "strict_small", "strict_block", "strict_pw", "strict_pw_unified", "inv_per_element", "inv_chunked", "inv_lone")
 
 
 class Form:
@@ -435,11 +437,12 @@ class Form:
     must have been created under.  hooks: the engine runs the test-hooks build.  staged: whether every launch of the call takes
     its LDS-staged kernel (None: the operation has no such kernel) -- checked against the test build's launch counter where
     the engine has one.  misalign: rows 8 bytes off a 16-byte boundary.  small: the independent-chain strict kernel, the one
-    how="small" names."""
+    how="small" names.  launch: the name of the zc::LaunchForm (LAUNCH_FORMS above) every call must be exactly
+    one launch of, by the test build's per-form counters (None: not checked)."""
 
-    def __init__(self, name, ops, lo=1, hi=1 << 40, env=None, hooks=False, staged=None, misalign=False, small=False):
+    def __init__(self, name, ops, lo=1, hi=1 << 40, env=None, hooks=False, staged=None, misalign=False, small=False, launch=None):
         self.name, self.ops, self.lo, self.hi, self.env = name, tuple(ops), lo, hi, dict(env or {})
-        self.hooks, self.staged, self.misalign, self.small = hooks, staged, misalign, small
+        self.hooks, self.staged, self.misalign, self.small, self.launch = hooks, staged, misalign, small, launch
 
 
 class EngineBackend:
@@ -447,12 +450,13 @@ class EngineBackend:
     default) -- an inversion case runs on the engine whose chunk it names, every other case on the default engine only.
     device: inputs as torch tensors on the GPU.  misalign: arrays that start 8 bytes off a 16-byte boundary.
     form: a `Form` -- only the cases of its operations run (the others have one form: None), at a batch size inside its range,
-    on device tensors so that one call is one launch; `how="small"` runs where the form is that kernel, and `counted` collects
-    (op, staged launches counted by the test build or None) per call."""
+    on device tensors so that one call is one launch; `how="small"` runs where the form is that kernel.  Per call, `counted`
+    collects (op, staged launches counted by the test build or None) and `forms` (op, {form name: launches} for the forms of
+    zc_launch_plan.h that the call launched, or None without the test build)."""
 
     def __init__(self, engine, chunk=None, device=False, misalign=False, form=None):
         self.e, self.chunk, self.device, self.misalign, self.form = engine, chunk, device, misalign, form
-        self.counted = []
+        self.counted, self.forms = [], []
         if form is not None:
             self.device, self.misalign = True, form.misalign
 
@@ -516,13 +520,23 @@ class EngineBackend:
         if self.form is not None:
             n = len(case.ins[0])
             assert self.form.lo <= n <= self.form.hi, "%s: %d rows do not reach the form '%s'" % (case.label(), n, self.form.name)
-        counter = getattr(self.e.lib, "zc_test_staged_launches", None)
-        c0 = counter(self.e.ctx) if counter else 0
+        c0 = self._launch_forms()
         got = fn(*[self._in(x) for x in case.ins], **{k: v for k, v in case.params.items() if k not in ("c", "lone")})
         if got is None:
             return None
-        self.counted.append((case.op, counter(self.e.ctx) - c0 if counter else None))
+        delta = None if c0 is None else {f: b - a for f, a, b in zip(LAUNCH_FORMS, c0, self._launch_forms()) if b != a}
+        self.counted.append((case.op, None if delta is None else delta.get("staged", 0)))
+        self.forms.append((case.op, delta))
         return tuple(self._host(x) for x in (got if isinstance(got, tuple) else (got,)))
+
+    def _launch_forms(self):
+        """The test build's launch counters per form of zc_launch_plan.h (None: the engine runs the product)."""
+        hook = getattr(self.e.lib, "zc_test_launch_forms", None)
+        if hook is None:
+            return None
+        counts = (C.c_uint64 * len(LAUNCH_FORMS))()
+        assert hook(self.e.ctx, counts, len(counts)) == 0
+        return list(counts)
 
     def op_mulmod(self, a, b, modl):
         return (self.e.sc_mul(a, b), self.e.sc_square(a)) if modl else (self.e.fe_mul(a, b), self.e.fe_square(a))

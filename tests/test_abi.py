@@ -68,8 +68,8 @@ def test_release_library_carries_no_test_hooks_and_reads_its_knobs_once(lib):
     assert "zc_test_" not in rel
     assert b"ZC_TEST_" not in open(z.LIB_PATH, "rb").read()
     tst = subprocess.check_output(["nm", "-D", "--defined-only", _lib.TEST_LIB_PATH], text=True)
-    assert {"zc_test_msm_sort", "zc_test_odd_table", "zc_test_staged_launches"} <= set(re.findall(r"\bT (zc_[a-z0-9_]+)", tst))
-    assert set(re.findall(r"\bT (zc_[a-z0-9_]+)", rel)) == set(re.findall(r"\bT (zc_[a-z0-9_]+)", tst)) - {"zc_test_msm_sort", "zc_test_odd_table", "zc_test_staged_launches"}
+    assert {"zc_test_msm_sort", "zc_test_odd_table", "zc_test_staged_launches", "zc_test_launch_forms"} <= set(re.findall(r"\bT (zc_[a-z0-9_]+)", tst))
+    assert set(re.findall(r"\bT (zc_[a-z0-9_]+)", rel)) == set(re.findall(r"\bT (zc_[a-z0-9_]+)", tst)) - {"zc_test_msm_sort", "zc_test_odd_table", "zc_test_staged_launches", "zc_test_launch_forms"}
     src = ""
     for f in os.listdir(os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")):
         if f.endswith((".hip", ".h")):

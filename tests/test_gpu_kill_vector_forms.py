@@ -3,11 +3,12 @@
 An operation with several kernels picks one by batch size, by a ZC_* knob of the context, by the alignment of its arrays --
 and, inside the stand-alone products, by a ballot over the wave.  The rows of tests/kill_vectors.py that the CPU tier proves
 to kill planted defects are tiled (Case.tiled: expected rows come along, no oracle run) to the smallest batch that reaches
-each form, on device tensors, so that one call is one launch of the kernel named here:
+each form, on device tensors, so that one call is one launch of the kernel named here (proven by the test build's counters, which
+count every answer of zc_launch_plan.h where the host code consumes it):
 
   strict scalar multiplication (group_core and recoding_fast `strict` -- and `small` where the form is that kernel -- and the
   rowwise recoding_tile cases, the two tiles the doubling gate must refuse among them)
-      k_ed_scalar_mul_small          independent column chains            2^14 + 1 rows     (size constants)
+      k_ed_scalar_mul_small          independent column chains            2^14 + 1 rows     (form counter)
       k_ed_scalar_mul                one workgroup per 256 rows           2^16 + 1
       k_ed_scalar_mul_pw             persistent waves                     2^17 + 77
       k_ed_scalar_mul_pw_unified     ZC_SCHED=unified                     2^17 + 77
@@ -42,11 +43,12 @@ pytestmark = pytest.mark.gpu
 
 PW_ROWS = T.PW_MIN_ELEMS + 77
 STRICT_FORMS = {f.name: (f, n) for f, n in (
-    (KV.Form("independent-chain kernel", KV.STRICT_OPS, lo=T.QUAD_LAUNCH_ELEMS + 1, hi=T.STRICT_SMALL_MAX_ELEMS, small=True), T.QUAD_LAUNCH_ELEMS + 1),
-    (KV.Form("one workgroup per 256 rows", KV.STRICT_OPS, lo=T.STRICT_SMALL_MAX_ELEMS + 1, hi=T.PW_MIN_ELEMS - 1), T.STRICT_SMALL_MAX_ELEMS + 1),
-    (KV.Form("persistent waves", KV.STRICT_OPS, lo=T.PW_MIN_ELEMS), PW_ROWS),
-    (KV.Form("persistent waves, ZC_SCHED=unified", KV.STRICT_OPS, lo=T.PW_MIN_ELEMS, env={"ZC_SCHED": "unified"}), PW_ROWS),
-    (KV.Form("ZC_SCHED=block at the persistent size", KV.STRICT_OPS, lo=T.PW_MIN_ELEMS, env={"ZC_SCHED": "block"}), PW_ROWS),
+    (KV.Form("independent-chain kernel", KV.STRICT_OPS, lo=T.QUAD_LAUNCH_ELEMS + 1, hi=T.STRICT_SMALL_MAX_ELEMS, small=True, hooks=True, launch="strict_small"),
+     T.QUAD_LAUNCH_ELEMS + 1),
+    (KV.Form("one workgroup per 256 rows", KV.STRICT_OPS, lo=T.STRICT_SMALL_MAX_ELEMS + 1, hi=T.PW_MIN_ELEMS - 1, hooks=True, launch="strict_block"), T.STRICT_SMALL_MAX_ELEMS + 1),
+    (KV.Form("persistent waves", KV.STRICT_OPS, lo=T.PW_MIN_ELEMS, hooks=True, launch="strict_pw"), PW_ROWS),
+    (KV.Form("persistent waves, ZC_SCHED=unified", KV.STRICT_OPS, lo=T.PW_MIN_ELEMS, env={"ZC_SCHED": "unified"}, hooks=True, launch="strict_pw_unified"), PW_ROWS),
+    (KV.Form("ZC_SCHED=block at the persistent size", KV.STRICT_OPS, lo=T.PW_MIN_ELEMS, env={"ZC_SCHED": "block"}, hooks=True, launch="strict_block"), PW_ROWS),
 )}
 STRICT_FAMILIES = ("group_core", "recoding_fast", "recoding_tile")
 POINT_ROWS = T.ED_STAGED_MIN_POINTS + 1
@@ -111,8 +113,10 @@ def test_strict_scalar_mul_forms(engines, families, name):
     cases = [c.tiled(n) for fam in STRICT_FAMILIES for c in families[fam] if c.rowwise and backend.takes(c)]
     made = run_form(backend, cases)
     assert made == (7 if form.small else 5), made                 # strict (+ small) of two families, the three rowwise tile cases
-    print("strict scalar-mul, %s: %d cases at n = %d (by size constants%s), %.2f s"
-          % (name, made, n, "".join(" and %s=%s" % kv for kv in form.env.items()), time.perf_counter() - t0))
+    # the test build's form counters: every call was exactly one launch, of the form this row names
+    assert len(backend.forms) == made and all(delta == {form.launch: 1} for _, delta in backend.forms), (name, backend.forms)
+    print("strict scalar-mul, %s: %d cases at n = %d%s (form counter: %s), %.2f s"
+          % (name, made, n, "".join(" and %s=%s" % kv for kv in form.env.items()), [delta for _, delta in backend.forms], time.perf_counter() - t0))
 
 
 @pytest.mark.parametrize("name", list(POINT_FORMS))

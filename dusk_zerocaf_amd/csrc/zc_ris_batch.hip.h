@@ -44,7 +44,27 @@ ZC_DI fe ris_dc_mul(const fe& x, const fe& y) { return ILP ? mont_mul_ilp<FP>(x,
 template <bool ILP>
 ZC_DI fe ris_dc_sqr(const fe& x) { return ILP ? mont_sqr_ilp<FP>(x) : mont_sqr<FP>(x); }
 
-// e, f, g, h and their products for the record at `row` (twenty words, any: a word's bits from 2^52 up are not read)
+// e, f, g, h and their products from the four coordinates X, Y, Z, T as residues with one common factor, each below 3N
+// (ris_dc_load's limbs below 1.5 N; a point in registers, R-class: products of operands below 3N stay below 1.02 N, their sums
+// below 2.04 N as the comments of ris_dc_finish want them)
+template <bool ILP>
+ZC_DI ris_dc_terms ris_dc_terms_of(const fe (&c)[4])
+{
+    ris_dc_terms t;
+    const fe xy = ris_dc_mul<ILP>(c[0], c[1]);
+    const fe zz = ris_dc_sqr<ILP>(c[2]);
+    const fe dtt = ris_dc_mul<ILP>(fe_const<FP>(ModP::D_M), ris_dc_sqr<ILP>(c[3]));
+    t.e = fe_add(xy, xy);
+    t.g = fe_add(ris_dc_sqr<ILP>(c[1]), ris_dc_sqr<ILP>(c[0]));
+    t.f = fe_add(zz, dtt);
+    t.h = fp_sub(zz, dtt);
+    t.eg = ris_dc_mul<ILP>(t.e, t.g);
+    t.fh = ris_dc_mul<ILP>(t.f, t.h);
+    t.w = ris_dc_mul<ILP>(t.eg, t.fh);
+    t.zero = fp_is_zero(t.w);
+    return t;
+}
+// ... for the record at `row` (twenty words, any: a word's bits from 2^52 up are not read)
 template <bool ILP>
 ZC_DI ris_dc_terms ris_dc_load(const u64* __restrict__ row)
 {
@@ -65,19 +85,7 @@ ZC_DI ris_dc_terms ris_dc_load(const u64* __restrict__ row)
 #pragma unroll
         for (int k = 0; k < 4; k++) c[k] = ris_dc_mul<ILP>(c[k], fe_one_m<FP>());
     }
-    ris_dc_terms t;
-    const fe xy = ris_dc_mul<ILP>(c[0], c[1]);
-    const fe zz = ris_dc_sqr<ILP>(c[2]);
-    const fe dtt = ris_dc_mul<ILP>(fe_const<FP>(ModP::D_M), ris_dc_sqr<ILP>(c[3]));
-    t.e = fe_add(xy, xy);
-    t.g = fe_add(ris_dc_sqr<ILP>(c[1]), ris_dc_sqr<ILP>(c[0]));
-    t.f = fe_add(zz, dtt);
-    t.h = fp_sub(zz, dtt);
-    t.eg = ris_dc_mul<ILP>(t.e, t.g);
-    t.fh = ris_dc_mul<ILP>(t.f, t.h);
-    t.w = ris_dc_mul<ILP>(t.eg, t.fh);
-    t.zero = fp_is_zero(t.w);
-    return t;
+    return ris_dc_terms_of<ILP>(c);
 }
 
 // The row's 32 bytes as four words from its terms and winv = 1 / w (Montgomery form, R-class); zeros for a row with w = 0.
@@ -107,6 +115,14 @@ ZC_DI void ris_double_compress_row(u64 (&out)[4], const u64* __restrict__ row)
 {
     const ris_dc_terms t = ris_dc_load<false>(row);
     ris_dc_finish<false>(out, t, fp_invert(t.w));                            // 0 -> 0, and the row's bytes are zeroed
+}
+// The same for a point that is in registers already (Montgomery form, R-class coordinates): the bytes of 2 Q (zc_shared.hip.h)
+template <bool ILP>
+ZC_DI void ris_double_compress_pt(u64 (&out)[4], const pt& Q)
+{
+    const fe c[4] = {Q.X, Q.Y, Q.Z, Q.T};
+    const ris_dc_terms t = ris_dc_terms_of<ILP>(c);
+    ris_dc_finish<ILP>(out, t, fp_invert(t.w));
 }
 
 // One lane's share of the batch: Montgomery's trick over w of the up to `c` rows lo, lo + stride, ... (as ed_to_affine_chunk:

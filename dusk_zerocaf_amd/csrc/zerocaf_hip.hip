@@ -30,6 +30,7 @@
 #include "zc_msm.hip.h"
 #include "zc_ris_batch.hip.h"
 #include "zc_hash.hip.h"
+#include "zc_shared.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -1594,6 +1595,48 @@ int zc_ris_roundtrip_mul(zc_ctx* ctx, const uint8_t* in32, const uint64_t* k, ui
                                dok ? dok + off : nullptr, table, ring, slots, (zc::u32)c);
         });
     }, ROWS(in32, 32), ROWS(k, 5), ROWS(out32, 32), OPT_ROWS(ok, 1));
+}
+
+// ---- one scalar for the whole batch (zerocaf_hip_ext_shared.h; kernels: zc_shared.hip.h, the host's recoding: zc_shared_scalar.h)
+// k is read here, before anything is queued: what travels to the device is the schedule, by value in the kernel arguments.
+static int shared_scalar_on_host(const uint64_t* k)
+{
+    Residency r = RES_HOST;
+    int d = -1;
+    residency_of(k, &r, &d);
+    if (r == RES_DEVICE) return fail(ZC_ERR_BAD_ARG, "k must be host memory");
+    return ZC_OK;
+}
+int zc_ed_scalar_mul_shared(zc_ctx* ctx, const uint64_t* p, const uint64_t* k, uint64_t* out, size_t n)
+{
+    REQUIRE(p);
+    REQUIRE(k);
+    REQUIRE(out);
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (n == 0) return ZC_OK;
+    if (int rc = shared_scalar_on_host(k)) return rc;
+    const zc::shared_schedule sched = zc::shared_schedule_ed(k);
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, u64* dout) {
+        return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ed_scalar_mul_shared, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), dp + 20 * off, sched, dout + 20 * off, table, ring, slots, (zc::u32)c);
+        });
+    }, ROWS(p, 20), ROWS(out, 20));
+}
+int zc_ris_mul_shared(zc_ctx* ctx, const uint8_t* in32, const uint64_t* k, uint8_t* out32, uint8_t* ok, size_t n)
+{
+    REQUIRE(in32);
+    REQUIRE(k);
+    REQUIRE(out32);
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (n == 0) return ZC_OK;
+    if (int rc = shared_scalar_on_host(k)) return rc;
+    const zc::shared_schedule sched = zc::shared_schedule_wire(k);          // of k' = (k mod L) / 2 mod L: the kernel encodes 2 (k' P)
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const uint8_t* din, uint8_t* dout, uint8_t* dok) {
+        return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ris_mul_shared, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), din + 32 * off, sched, dout + 32 * off, dok ? dok + off : nullptr,
+                               table, ring, slots, (zc::u32)c);
+        });
+    }, ROWS(in32, 32), ROWS(out32, 32), OPT_ROWS(ok, 1));
 }
 
 // ---- "next" rows (N3, N4)

@@ -19,6 +19,7 @@ from . import _lib
 from .hash_batch import HashMixin
 from .ristretto_batch import RistrettoBatchMixin
 from .scalar_ext import ScalarExtMixin
+from .shared_scalar import SharedScalarMixin
 
 STRICT = 0          # double_and_add (Mul<Scalar>)
 LTR_BIN = 1         # ltr_bin_mul
@@ -44,7 +45,7 @@ def _one_call(method):
     return locked
 
 
-class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin):
+class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin, SharedScalarMixin):
     """One zc_ctx.  `devices=None` = one slot on torch's current device when torch is loaded and sees a GPU; otherwise
     zc_ctx_create(NULL, 0): the calling thread's current HIP device (whatever hipSetDevice chose), read back from the
     context.  The context reads the library's tuning knobs (ZC_* environment variables)

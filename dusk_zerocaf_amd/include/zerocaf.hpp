@@ -774,6 +774,31 @@ inline std::pair<CompressedRistretto, std::vector<uint8_t>> ris_lincomb_sum(cons
     std::memcpy(out.bytes.data(), o, 32);
     return {out, ok};
 }
+// ONE scalar for a whole batch (zc_ed_scalar_mul_shared / zc_ris_mul_shared, zerocaf_hip_ext_shared.h through zerocaf_hip_ext.h): a view
+// key against every output, an OPRF key against every client point.  The scalar is recoded once on the host; the running time
+// depends on it.  ps[i] * k under == (identical encodings, another projective representative than the reference's).
+inline std::vector<EdwardsPoint> scalar_mul_shared(const std::vector<EdwardsPoint>& ps, const Scalar& k)
+{
+    std::vector<uint64_t> p(ps.size() * 20), o(ps.size() * 20);
+    for (size_t i = 0; i < ps.size(); i++) ps[i].flat(&p[20 * i]);
+    if (!ps.empty()) Backend::check(zc_ed_scalar_mul_shared(Backend::ctx(), p.data(), k.l.data(), o.data(), ps.size()), "zc_ed_scalar_mul_shared");
+    std::vector<EdwardsPoint> out(ps.size());
+    for (size_t i = 0; i < ps.size(); i++) out[i] = EdwardsPoint::unflat(&o[20 * i]);
+    return out;
+}
+// compress(k * decompress(es[i])), byte-identical to the reference's composition.  first: the encodings (32 zero bytes where a
+// row did not decode, or where the product is the identity), second: the accept mask.
+inline std::pair<std::vector<CompressedRistretto>, std::vector<uint8_t>> ris_mul_shared(const std::vector<CompressedRistretto>& es, const Scalar& k)
+{
+    const size_t n = es.size();
+    std::vector<uint8_t> e(n * 32), o(n * 32), ok(n);
+    for (size_t i = 0; i < n; i++) std::memcpy(&e[32 * i], es[i].bytes.data(), 32);
+    std::vector<CompressedRistretto> out(n);
+    if (n == 0) return {out, ok};
+    Backend::check(zc_ris_mul_shared(Backend::ctx(), e.data(), k.l.data(), o.data(), ok.data(), n), "zc_ris_mul_shared");
+    for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
+    return {out, ok};
+}
 // SHA-512 over batched rows (zc_sha512_rows / zc_sc_from_sha512 / zc_ris_from_sha512, zerocaf_hip_ext_hash.h through
 // zerocaf_hip_ext.h): the message of row i is prefix || parts[0][i] || parts[1][i] || ..., parts[j] = n rows of part_len[j]
 // contiguous bytes (1..4 parts, a prefix of at most 256 bytes, rows of at most 65535).  Host or device pointers, all of one kind.

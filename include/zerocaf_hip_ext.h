@@ -41,5 +41,6 @@ int zc_ris_double_and_compress(zc_ctx *ctx, const uint64_t *p, uint8_t *out32, s
 /* Calls that reduce a whole batch to one result have a header of their own, which comes in with this one. */
 #include "zerocaf_hip_ext_sum.h"
 #include "zerocaf_hip_ext_hash.h"
+#include "zerocaf_hip_ext_shared.h"
 
 #endif /* ZEROCAF_HIP_EXT_H */

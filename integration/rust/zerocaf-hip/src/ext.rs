@@ -1,16 +1,17 @@
 //! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h` / `zerocaf_hip_ext_hash.h`,
-//! which it includes).
+//! which it includes).  The calls with one scalar for a whole batch (`zerocaf_hip_ext_shared.h`, included likewise) are at the end.
 //!
 //! `ffi.rs` is the rendering of `zerocaf_hip.h` and stays exactly that; calls declared in the second header are bound here,
 //! with their own `extern "C"` block and a safe wrapper each.
 
 use std::os::raw::c_int;
 
+use zerocaf::edwards::EdwardsPoint;
 use zerocaf::ristretto::{CompressedRistretto, RistrettoPoint};
 use zerocaf::scalar::Scalar;
 
 use super::ffi::ZcCtx;
-use super::{bytes32, check, flat_ris, flat_sc, HipBackend, Result};
+use super::{bytes32, check, flat_ed, flat_ris, flat_sc, masked, unflat_ed, HipBackend, Result};
 
 extern "C" {
     /// `out32[i] = RistrettoPoint(2 * P_i).compress()`; see `zerocaf_hip_ext.h`.
@@ -23,6 +24,10 @@ extern "C" {
     pub fn zc_sc_from_sha512(ctx: *mut ZcCtx, prefix: *const u8, prefix_len: usize, parts: *const *const u8, part_len: *const usize, nparts: usize, out: *mut u64, n: usize) -> c_int;
     /// `out[i]` = `from_uniform_bytes` of that digest, twenty limbs: `zc_ris_from_uniform_bytes` likewise.
     pub fn zc_ris_from_sha512(ctx: *mut ZcCtx, prefix: *const u8, prefix_len: usize, parts: *const *const u8, part_len: *const usize, nparts: usize, out: *mut u64, n: usize) -> c_int;
+    /// `out[i] = k * P_i` for ONE scalar `k` (five words in host memory); see `zerocaf_hip_ext_shared.h`.
+    pub fn zc_ed_scalar_mul_shared(ctx: *mut ZcCtx, p: *const u64, k: *const u64, out: *mut u64, n: usize) -> c_int;
+    /// `out32[i] = compress(k * decompress(in32[i]))` for ONE scalar `k` (five words in host memory); see `zerocaf_hip_ext_shared.h`.
+    pub fn zc_ris_mul_shared(ctx: *mut ZcCtx, in32: *const u8, k: *const u64, out32: *mut u8, ok: *mut u8, n: usize) -> c_int;
 }
 
 /// The message arguments of the three SHA-512 calls from `parts[j]` = n rows of `part_len[j]` contiguous bytes: (pointers, lengths, n).
@@ -110,5 +115,31 @@ impl HipBackend {
             check(unsafe { zc_ris_from_sha512(self.ctx, prefix.as_ptr(), prefix.len(), ptrs.as_ptr(), lens.as_ptr(), lens.len(), out.as_mut_ptr(), n) })?;
         }
         Ok(out.chunks_exact(20).map(|c| { let mut p = [0u64; 20]; p.copy_from_slice(c); p }).collect())
+    }
+
+    /// `p[i] * k` for every point and ONE scalar (a view key, an OPRF key): the same group elements as `scalar_mul` with `k`
+    /// in every row -- equal under `==`, identical encodings, another projective representative -- on a schedule recoded
+    /// once on the host.  The running time depends on `k`.
+    pub fn ed_scalar_mul_shared(&self, p: &[EdwardsPoint], k: &Scalar) -> Result<Vec<EdwardsPoint>> {
+        let (fp, n) = (flat_ed(p), p.len());
+        let mut out = vec![0u64; n * 20];
+        if n > 0 {
+            check(unsafe { zc_ed_scalar_mul_shared(self.ctx, fp.as_ptr(), k.0.as_ptr(), out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_ed(&out))
+    }
+
+    /// `(c[i].decompress()? * k).compress()` for every encoding and ONE scalar, byte-identical to `ris_roundtrip_mul` with `k`
+    /// in every row; `None` where an encoding does not decode.  No square root on the way out: the call multiplies by
+    /// `k / 2 mod L` and encodes the double.
+    pub fn ris_mul_shared(&self, c: &[CompressedRistretto], k: &Scalar) -> Result<Vec<Option<CompressedRistretto>>> {
+        let flat: Vec<u8> = c.iter().flat_map(|e| e.0.iter().copied()).collect();
+        let n = c.len();
+        let (mut out, mut ok) = (vec![0u8; n * 32], vec![0u8; n]);
+        if n > 0 {
+            check(unsafe { zc_ris_mul_shared(self.ctx, flat.as_ptr(), k.0.as_ptr(), out.as_mut_ptr(), ok.as_mut_ptr(), n) })?;
+        }
+        let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
+        Ok(masked(enc, &ok))
     }
 }

@@ -14,7 +14,7 @@ DEPS = ["zerocaf_hip.hip", "zc_kernels.hip.h", "zc_msm.hip.h", "zc_msm_plan.h", 
         "zc_constants.hip.h", "zc_ris_batch.hip.h", "zc_hash.hip.h", "zc_shared.hip.h", "zc_shared_scalar.h",
         os.path.join("..", "..", "include", "zerocaf_hip.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext.h"),
         os.path.join("..", "..", "include", "zerocaf_hip_ext_sum.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext_hash.h"),
-        os.path.join("..", "..", "include", "zerocaf_hip_ext_shared.h")]
+        os.path.join("..", "..", "include", "zerocaf_hip_ext_shared.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext_shared_lincomb.h")]
 
 
 def hipcc() -> str:

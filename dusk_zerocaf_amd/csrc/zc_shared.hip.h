@@ -94,6 +94,91 @@ ZC_DI void shared_ris_encode(u64 (&w)[4], const pt& Q, bool dec)
     if (!dec) w[0] = w[1] = w[2] = w[3] = 0;
 }
 
+// ---------------------------------------------------------------- a scalar VECTOR for the batch: out[i] = sum_j k_j P_ij
+// zc_ed_lincomb_shared / zc_ris_lincomb_shared.  The host merges the terms' recodings into one schedule (zc_shared_scalar.h:
+// shared_lincomb_schedule): one doubling chain and one cached addition per non-zero digit of ANY term, about 252 * 7 +
+// 43.5 * 10 t multiplications per row against the 1 827 + 567 t of lincomb_fast with its per-lane digits.  Term j's table
+// {1, 3, .., 15} P_ij lies in unit j of the wave's slot (`tables.term(j)`), built only as far as the schedule reads it.
+
+// table[j] = (2 j + 1) P for j < entries (wave-uniform): shared_table_build cut short.  entries = 1 (k_j = +-2^e, the
+// coefficient 1 of an ElGamal decryption) costs one conversion, entries = 0 (k_j = 0) nothing.  The records are
+// shared_table_build's own whatever the bound, so one term gives the limbs of the single-scalar call.
+template <class TABLE>
+ZC_DI void shared_table_build_upto(const pt& P, const TABLE table, u32 entries)
+{
+    if (entries == 0) return;
+    niels_store(table.entry(0), niels_from_pt(P));
+    if (entries == 1) return;
+    const niels c2 = niels_from_pt(pt_double_fast<true>(P));
+    pt q = P;
+#pragma unroll 1
+    for (u32 j = 1; j < entries; j++) {
+        q = pt_add_cached(q, c2);
+        niels_store(table.entry((int)j), niels_from_pt(q));
+    }
+}
+// shared_steps with a term index.  A step without doublings (two terms with a digit at one position) takes T from the
+// addition before it: pt_add_cached returns all four coordinates.
+template <bool ILP, class TABLES>
+ZC_DI pt shared_lincomb_steps(const TABLES tables, const shared_lincomb_schedule& s)
+{
+    pt Q = pt_identity();
+    for (u32 i = 0; i < s.steps; i++) {
+        const u32 w = s.step[i];
+        Q = shared_doublings<ILP>(Q, shared_step_doublings(w));
+        const int d = shared_step_digit(w);
+        niels c = niels_load(tables.term((int)shared_step_term(w)).entry((d < 0 ? -d : d) >> 1));
+        if (d < 0) {                                      // -c, decided per wave (see shared_steps)
+            const fe ymx = c.ymx;
+            c.ymx = c.ypx;
+            c.ypx = ymx;
+            c.t2d = fe_neg_lazy<FP>(c.t2d);
+        }
+        Q = pt_add_cached<ILP>(Q, c);
+    }
+    return Q;
+}
+template <class TABLES>
+ZC_DI pt shared_lincomb_sum(const TABLES tables, const shared_lincomb_schedule& s)
+{
+    return zc_small_launch() ? shared_lincomb_steps<true>(tables, s) : shared_lincomb_steps<false>(tables, s);
+}
+ZC_DI pt shared_lincomb_tail(const pt& Q, const shared_lincomb_schedule& s)
+{
+    return zc_small_launch() ? shared_doublings<true>(Q, s.tail) : shared_doublings<false>(Q, s.tail);
+}
+// The wire form's terms, as ris_lincomb_decode / ris_lincomb_table (zc_curve.hip.h) handle them: a decoded point (Z = 1)
+// waits as X | Y | T in the first record of its own table, which the build then overwrites.  An undecodable term is parked
+// as the identity, so its lane walks the schedule with curve points; the row leaves as zero bytes.
+template <class TABLE>
+ZC_DI bool shared_lincomb_decode(const u64 (&w)[4], const TABLE table)
+{
+    pt P;
+    const bool dec = shared_ris_decode(P, w);
+    u32* e = table.entry(0);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        e[k] = P.X.v[k];
+        e[9 + k] = P.Y.v[k];
+        e[18 + k] = P.T.v[k];
+    }
+    return dec;
+}
+template <class TABLE>
+ZC_DI void shared_lincomb_table(const TABLE table, u32 entries)
+{
+    pt P;
+    const u32* e = table.entry(0);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        P.X.v[k] = e[k];
+        P.Y.v[k] = e[9 + k];
+        P.T.v[k] = e[18 + k];
+    }
+    P.Z = fe_one_m<FP>();
+    shared_table_build_upto(P, table, entries);
+}
+
 }  // namespace zc
 
 // the kernels: hipcc only (the host emulation of the test tier builds the device functions above with a C++ compiler)
@@ -150,6 +235,84 @@ ZC_KERNEL_3W void k_ris_mul_shared(const uint8_t* in, const shared_schedule sche
     pt Q = shared_mul_steps(P, mine, sched);
     ring_release(ring, hold + wave_in_block);
     Q = shared_mul_tail(Q, sched);
+    shared_ris_encode(w, Q, dec);
+    const u32 i_late = wave_first + lane_id_fresh();
+    if (i_late < n) {
+        store_words256(out + 32 * (size_t)i_late, w);
+        if (ok) ok[i_late] = dec ? 1 : 0;
+    }
+}
+
+// ---- a scalar vector for the batch: out[i] = sum_j k_j P_ij (zc_ed_lincomb_shared, zc_ris_lincomb_shared) ----------
+// One row per lane; the wave's slot is sched.terms consecutive units of the ring, re-based as k_ed_lincomb does it
+// (ring_table_terms).  No LDS beyond the ring's `hold` words at any term count -- the digits are the schedule's, in scalar
+// registers -- so the workgroup has 256 lanes throughout.  The slot goes back after the last addition; the tail doublings
+// need no table.
+ZC_KERNEL_3W void k_ed_lincomb_shared(const u64* p, const shared_lincomb_schedule sched, u64* out, u32* table, u32* ring, u32 ring_slots, u32 units_per_xcd,
+                                      u32 n)
+{
+    const u32 wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 wave_first = blockIdx.x * ZC_BLOCK + wave_in_block * 64u;
+    __shared__ u32 hold[ZC_BLOCK / 64];
+    const ring_table got = ring_acquire(table, ring, hold + wave_in_block, ring_slots);
+    if (!got.base) {                                       // the wave gave up waiting for its table slot (wave-uniform): poison, no barrier follows
+        const u32 i = wave_first + lane_id_fresh();
+        if (i < n)
+            for (int j = 0; j < 20; j++) out[20 * (size_t)i + j] = ~(u64)0;
+        return;
+    }
+    const u32 terms = sched.terms;
+    const u32 named = (u32)((size_t)(got.base - table) / (64 * 256));          // xcc * RING_SLOTS + slot (wave-uniform)
+    const u32 xcc = named / RING_SLOTS, slot = named % RING_SLOTS;
+    const ring_table_terms mine{table + (size_t)(xcc * units_per_xcd + slot * terms) * (64 * 256)};
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) {
+        const u32 row = wave_first + lane_id_fresh();
+        const u32 entries = sched.entries[j];              // wave-uniform: a term the schedule never reads is not even loaded
+        if (entries) shared_table_build_upto(pt_load(p + 20 * ((size_t)(row < n ? row : 0) * terms + j)), mine.term((int)j), entries);
+    }
+    pt Q = shared_lincomb_sum(mine, sched);
+    ring_release(ring, hold + wave_in_block);              // the last table read is behind us
+    Q = shared_lincomb_tail(Q, sched);
+    const u32 i_late = wave_first + lane_id_fresh();
+    if (i_late < n) pt_store(out + 20 * (size_t)i_late, Q);
+}
+// bytes in, bytes out over the schedule of the k'_j.  Decoding and table building are two `unroll 1` loops for the reason
+// given above k_ris_lincomb (zc_kernels.hip.h); a term under a zero scalar builds nothing but is decoded, for the accept flag.
+ZC_KERNEL_3W void k_ris_lincomb_shared(const uint8_t* in, const shared_lincomb_schedule sched, uint8_t* out, uint8_t* ok, u32* table, u32* ring, u32 ring_slots,
+                                       u32 units_per_xcd, u32 n)
+{
+    const u32 wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 wave_first = blockIdx.x * ZC_BLOCK + wave_in_block * 64u;
+    __shared__ u32 hold[ZC_BLOCK / 64];
+    const ring_table got = ring_acquire(table, ring, hold + wave_in_block, ring_slots);
+    if (!got.base) {                                       // the wave gave up waiting for its table slot (wave-uniform): poison, no barrier follows
+        const u32 i = wave_first + lane_id_fresh();
+        if (i < n) {
+            const u64 ones[4] = {~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0};
+            store_words256(out + 32 * (size_t)i, ones);
+            if (ok) ok[i] = 0;
+        }
+        return;
+    }
+    const u32 terms = sched.terms;
+    const u32 named = (u32)((size_t)(got.base - table) / (64 * 256));          // xcc * RING_SLOTS + slot (wave-uniform)
+    const u32 xcc = named / RING_SLOTS, slot = named % RING_SLOTS;
+    const ring_table_terms mine{table + (size_t)(xcc * units_per_xcd + slot * terms) * (64 * 256)};
+    bool dec = true;                                       // the only per-lane value that survives a decode
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) {
+        const u32 row = wave_first + lane_id_fresh();
+        u64 w[4];
+        load_words256(w, in + 32 * ((size_t)(row < n ? row : 0) * terms + j));
+        dec = shared_lincomb_decode(w, mine.term((int)j)) && dec;
+    }
+#pragma unroll 1
+    for (u32 j = 0; j < terms; j++) shared_lincomb_table(mine.term((int)j), sched.entries[j]);
+    pt Q = shared_lincomb_sum(mine, sched);
+    ring_release(ring, hold + wave_in_block);
+    Q = shared_lincomb_tail(Q, sched);
+    u64 w[4];
     shared_ris_encode(w, Q, dec);
     const u32 i_late = wave_first + lane_id_fresh();
     if (i_late < n) {

@@ -161,4 +161,75 @@ inline shared_schedule shared_schedule_wire(const uint64_t* k)
     return shared_recode(shared_half_mod_l(shared_from_limbs52(l)));
 }
 
+// ---------------------------------------------------------------- a scalar VECTOR for the batch (zc_ed_lincomb_shared / zc_ris_lincomb_shared)
+// out[i] = sum_j k_j P_ij with the k_j shared by every row: each term is recoded as above and the digits of all terms are
+// merged into ONE list from the top position down -- one doubling chain, one cached addition per non-zero digit of any term.
+// A step word is shared_schedule's with the term index in its spare bits 24..31; two terms with a digit at the same position
+// give a step with 0 doublings in front (ties in term order).  At most 53 * terms steps.  entries[j]: how many records of
+// term j's table {1, 3, .., 15} P_ij the schedule reads, (max |d| + 1) / 2 -- 0 for a zero scalar, 1 for +-2^e -- so that
+// the kernels build no more than that.  1 740 bytes, by value in the kernel arguments like shared_schedule.
+constexpr int SHARED_LINCOMB_MAX_TERMS = 8;
+constexpr int SHARED_LINCOMB_MAX_STEPS = SHARED_MAX_STEPS * SHARED_LINCOMB_MAX_TERMS;
+struct shared_lincomb_schedule {
+    uint32_t steps;                                    // additions, 0 .. 53 * terms
+    uint32_t tail;                                     // doublings after the last addition
+    uint32_t terms;                                    // 1 .. 8
+    uint32_t entries[SHARED_LINCOMB_MAX_TERMS];        // table records term j needs, 0 .. 8
+    uint32_t step[SHARED_LINCOMB_MAX_STEPS];
+};
+static_assert(sizeof(shared_lincomb_schedule) == 4 * (3 + SHARED_LINCOMB_MAX_TERMS + SHARED_LINCOMB_MAX_STEPS), "a POD of 32-bit words");
+static_assert(sizeof(shared_lincomb_schedule) + 256 <= 2048, "the schedule and the other kernel arguments stay well under the 4 KB of kernel arguments");
+constexpr uint32_t shared_lincomb_step_word(unsigned doublings, int digit, unsigned term) { return shared_step_word(doublings, digit) | ((uint32_t)term << 24); }
+constexpr unsigned shared_step_term(uint32_t w) { return w >> 24; }
+
+// The merge of the terms' schedules.  Term j's digit positions follow from its tail and its doublings; the next step is
+// always the highest position any term still holds, the lowest term index first.
+inline shared_lincomb_schedule shared_lincomb_merge(const shared_schedule* per_term, size_t terms)
+{
+    shared_lincomb_schedule s = {};
+    if (terms > (size_t)SHARED_LINCOMB_MAX_TERMS) terms = SHARED_LINCOMB_MAX_TERMS;       // the entry points refuse such a call
+    s.terms = (uint32_t)terms;
+    int pos[SHARED_LINCOMB_MAX_TERMS][SHARED_MAX_STEPS];
+    uint32_t at[SHARED_LINCOMB_MAX_TERMS];
+    for (size_t j = 0; j < terms; j++) {
+        const shared_schedule& t = per_term[j];
+        int p = (int)t.tail, maxabs = 0;
+        for (int i = (int)t.steps - 1; i >= 0; i--) {
+            pos[j][i] = p;
+            p += (int)shared_step_doublings(t.step[i]);
+            const int d = shared_step_digit(t.step[i]), a = d < 0 ? -d : d;
+            maxabs = a > maxabs ? a : maxabs;
+        }
+        s.entries[j] = (uint32_t)((maxabs + 1) / 2);
+        at[j] = 0;
+    }
+    int last = 0;
+    for (;;) {
+        int best = -1;
+        for (size_t j = 0; j < terms; j++)
+            if (at[j] < per_term[j].steps && (best < 0 || pos[j][at[j]] > pos[best][at[best]])) best = (int)j;
+        if (best < 0) break;
+        const int p = pos[best][at[best]];
+        s.step[s.steps] = shared_lincomb_step_word(s.steps ? (unsigned)(last - p) : 0u, shared_step_digit(per_term[best].step[at[best]]), (unsigned)best);
+        s.steps++;
+        at[best]++;
+        last = p;
+    }
+    s.tail = (uint32_t)last;
+    return s;
+}
+// k: terms * 5 words.  The Edwards form walks the k_eff,j themselves, the wire form the k'_j = (k_eff,j mod L) / 2 mod L.
+inline shared_lincomb_schedule shared_lincomb_schedule_ed(const uint64_t* k, size_t terms)
+{
+    shared_schedule per_term[SHARED_LINCOMB_MAX_TERMS];
+    for (size_t j = 0; j < terms && j < (size_t)SHARED_LINCOMB_MAX_TERMS; j++) per_term[j] = shared_schedule_ed(k + 5 * j);
+    return shared_lincomb_merge(per_term, terms);
+}
+inline shared_lincomb_schedule shared_lincomb_schedule_wire(const uint64_t* k, size_t terms)
+{
+    shared_schedule per_term[SHARED_LINCOMB_MAX_TERMS];
+    for (size_t j = 0; j < terms && j < (size_t)SHARED_LINCOMB_MAX_TERMS; j++) per_term[j] = shared_schedule_wire(k + 5 * j);
+    return shared_lincomb_merge(per_term, terms);
+}
+
 }  // namespace zc

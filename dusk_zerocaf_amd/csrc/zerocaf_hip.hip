@@ -1638,6 +1638,52 @@ int zc_ris_mul_shared(zc_ctx* ctx, const uint8_t* in32, const uint64_t* k, uint8
         });
     }, ROWS(in32, 32), ROWS(out32, 32), OPT_ROWS(ok, 1));
 }
+// ---- one scalar VECTOR for the whole batch (zerocaf_hip_ext_shared_lincomb.h): out[i] = sum_j k_j * P_ij.  The terms' recodings
+// are merged into one schedule here (zc_shared_scalar.h: shared_lincomb_schedule), which travels by value like the single
+// scalar's.  Ring geometry is zc_ed_lincomb's (one 64 KB unit per term and wave slot); the kernels keep no digits in LDS, so
+// every term count runs 256-lane workgroups without dynamic LDS.
+static int shared_lincomb_args(const char* who, size_t terms, size_t n)
+{
+    if (terms < 1 || terms > ZC_LINCOMB_MAX_TERMS) return failf(ZC_ERR_BAD_ARG, "%s: terms must be 1..ZC_LINCOMB_MAX_TERMS", who);
+    if (n >= ((size_t)1 << 31) / terms + (((size_t)1 << 31) % terms != 0)) return failf(ZC_ERR_BAD_ARG, "%s: n * terms must stay below 2^31", who);
+    return ZC_OK;
+}
+int zc_ed_lincomb_shared(zc_ctx* ctx, const uint64_t* points, const uint64_t* k, size_t terms, uint64_t* out, size_t n)
+{
+    REQUIRE(points);
+    REQUIRE(k);
+    REQUIRE(out);
+    if (int rc = shared_lincomb_args("zc_ed_lincomb_shared", terms, n)) return rc;
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (n == 0) return ZC_OK;
+    if (int rc = shared_scalar_on_host(k)) return rc;
+    const zc::shared_lincomb_schedule sched = zc::shared_lincomb_schedule_ed(k, terms);
+    const zc::u32 units = (zc::u32)zc::ring_units_per_xcd(terms);
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, u64* dout) {
+        return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ed_lincomb_shared, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), dp + 20 * terms * off, sched, dout + 20 * off, table, ring, slots,
+                               units, (zc::u32)c);
+        }, terms);
+    }, ROWS(points, 20 * terms), ROWS(out, 20));
+}
+int zc_ris_lincomb_shared(zc_ctx* ctx, const uint8_t* in32, const uint64_t* k, size_t terms, uint8_t* out32, uint8_t* ok, size_t n)
+{
+    REQUIRE(in32);
+    REQUIRE(k);
+    REQUIRE(out32);
+    if (int rc = shared_lincomb_args("zc_ris_lincomb_shared", terms, n)) return rc;
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (n == 0) return ZC_OK;
+    if (int rc = shared_scalar_on_host(k)) return rc;
+    const zc::shared_lincomb_schedule sched = zc::shared_lincomb_schedule_wire(k, terms);    // of the k'_j: the kernel encodes 2 (sum k'_j P_j)
+    const zc::u32 units = (zc::u32)zc::ring_units_per_xcd(terms);
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const uint8_t* din, uint8_t* dout, uint8_t* dok) {
+        return fast_ring(D, cnt, [&](zc::u32* table, zc::u32* ring, zc::u32 slots, size_t off, size_t c) {
+            hipLaunchKernelGGL(zc::k_ris_lincomb_shared, dim3(grid_for(c)), dim3(zc::ZC_BLOCK), 0, D.s(), din + 32 * terms * off, sched, dout + 32 * off,
+                               dok ? dok + off : nullptr, table, ring, slots, units, (zc::u32)c);
+        }, terms);
+    }, ROWS(in32, 32 * terms), ROWS(out32, 32), OPT_ROWS(ok, 1));
+}
 
 // ---- "next" rows (N3, N4)
 int zc_ed_is_valid(zc_ctx* ctx, const uint64_t* p, uint8_t* valid, size_t n) { return batched(ctx, n, false, plain(zc::k_ed_is_valid), ROWS(p, 20), ROWS(valid, 1)); }

@@ -799,6 +799,44 @@ inline std::pair<std::vector<CompressedRistretto>, std::vector<uint8_t>> ris_mul
     for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
     return {out, ok};
 }
+// ONE scalar VECTOR for a whole batch (zc_ed_lincomb_shared / zc_ris_lincomb_shared, zerocaf_hip_ext_shared_lincomb.h through
+// zerocaf_hip_ext.h): out[i] = sum_j ks[j] * pss[i][j] with the same 1..8 coefficients in every row -- ElGamal decryption under one
+// key (1, -x), threshold share combination (the Lagrange coefficients), generator folding (u^-1, u).  The terms' recodings are merged
+// into one schedule on the host; the running time depends on ks.  Row i equals ((k0*P0 + k1*P1) + ...) under ==.
+inline std::vector<EdwardsPoint> ed_lincomb_shared(const std::vector<std::vector<EdwardsPoint>>& pss, const std::vector<Scalar>& ks)
+{
+    const size_t n = pss.size(), t = ks.size();
+    std::vector<uint64_t> p(n * t * 20), k(t * 5), o(n * 20);
+    for (size_t j = 0; j < t; j++) std::memcpy(&k[5 * j], ks[j].l.data(), 40);
+    for (size_t i = 0; i < n; i++) {
+        if (pss[i].size() != t) throw std::invalid_argument("ed_lincomb_shared: a row without one point per scalar");
+        for (size_t j = 0; j < t; j++) pss[i][j].flat(&p[20 * (i * t + j)]);
+    }
+    if (n) Backend::check(zc_ed_lincomb_shared(Backend::ctx(), p.data(), k.data(), t, o.data(), n), "zc_ed_lincomb_shared");
+    std::vector<EdwardsPoint> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = EdwardsPoint::unflat(&o[20 * i]);
+    return out;
+}
+// compress(sum_j ks[j] * decompress(ess[i][j])), byte-identical to ris_lincomb without a base term and with ks in every row.
+// first: the encodings (32 zero bytes where a term did not decode, or where the sum is the identity), second: the accept mask.
+// No basepoint term: pass the encoding of B as a term.
+inline std::pair<std::vector<CompressedRistretto>, std::vector<uint8_t>> ris_lincomb_shared(const std::vector<std::vector<CompressedRistretto>>& ess,
+                                                                                            const std::vector<Scalar>& ks)
+{
+    const size_t n = ess.size(), t = ks.size();
+    std::vector<uint8_t> e(n * t * 32), o(n * 32), ok(n);
+    std::vector<uint64_t> k(t * 5);
+    for (size_t j = 0; j < t; j++) std::memcpy(&k[5 * j], ks[j].l.data(), 40);
+    for (size_t i = 0; i < n; i++) {
+        if (ess[i].size() != t) throw std::invalid_argument("ris_lincomb_shared: a row without one encoding per scalar");
+        for (size_t j = 0; j < t; j++) std::memcpy(&e[32 * (i * t + j)], ess[i][j].bytes.data(), 32);
+    }
+    std::vector<CompressedRistretto> out(n);
+    if (n == 0) return {out, ok};
+    Backend::check(zc_ris_lincomb_shared(Backend::ctx(), e.data(), k.data(), t, o.data(), ok.data(), n), "zc_ris_lincomb_shared");
+    for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
+    return {out, ok};
+}
 // SHA-512 over batched rows (zc_sha512_rows / zc_sc_from_sha512 / zc_ris_from_sha512, zerocaf_hip_ext_hash.h through
 // zerocaf_hip_ext.h): the message of row i is prefix || parts[0][i] || parts[1][i] || ..., parts[j] = n rows of part_len[j]
 // contiguous bytes (1..4 parts, a prefix of at most 256 bytes, rows of at most 65535).  Host or device pointers, all of one kind.

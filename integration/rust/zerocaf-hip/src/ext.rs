@@ -1,5 +1,6 @@
 //! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h` / `zerocaf_hip_ext_hash.h`,
-//! which it includes).  The calls with one scalar for a whole batch (`zerocaf_hip_ext_shared.h`, included likewise) are at the end.
+//! which it includes).  The calls with one scalar for a whole batch (`zerocaf_hip_ext_shared.h`, included likewise) and with one
+//! scalar vector for a whole batch (`zerocaf_hip_ext_shared_lincomb.h`) are at the end.
 //!
 //! `ffi.rs` is the rendering of `zerocaf_hip.h` and stays exactly that; calls declared in the second header are bound here,
 //! with their own `extern "C"` block and a safe wrapper each.
@@ -28,6 +29,10 @@ extern "C" {
     pub fn zc_ed_scalar_mul_shared(ctx: *mut ZcCtx, p: *const u64, k: *const u64, out: *mut u64, n: usize) -> c_int;
     /// `out32[i] = compress(k * decompress(in32[i]))` for ONE scalar `k` (five words in host memory); see `zerocaf_hip_ext_shared.h`.
     pub fn zc_ris_mul_shared(ctx: *mut ZcCtx, in32: *const u8, k: *const u64, out32: *mut u8, ok: *mut u8, n: usize) -> c_int;
+    /// `out[i] = sum_j k_j * P_ij` for ONE scalar vector `k` (`terms * 5` words in host memory); see `zerocaf_hip_ext_shared_lincomb.h`.
+    pub fn zc_ed_lincomb_shared(ctx: *mut ZcCtx, points: *const u64, k: *const u64, terms: usize, out: *mut u64, n: usize) -> c_int;
+    /// `out32[i] = compress(sum_j k_j * decompress(in32[i][j]))` for ONE scalar vector `k`; see `zerocaf_hip_ext_shared_lincomb.h`.
+    pub fn zc_ris_lincomb_shared(ctx: *mut ZcCtx, in32: *const u8, k: *const u64, terms: usize, out32: *mut u8, ok: *mut u8, n: usize) -> c_int;
 }
 
 /// The message arguments of the three SHA-512 calls from `parts[j]` = n rows of `part_len[j]` contiguous bytes: (pointers, lengths, n).
@@ -138,6 +143,37 @@ impl HipBackend {
         let (mut out, mut ok) = (vec![0u8; n * 32], vec![0u8; n]);
         if n > 0 {
             check(unsafe { zc_ris_mul_shared(self.ctx, flat.as_ptr(), k.0.as_ptr(), out.as_mut_ptr(), ok.as_mut_ptr(), n) })?;
+        }
+        let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
+        Ok(masked(enc, &ok))
+    }
+
+    /// `sum_j k[j] * p[i][j]` for every row and ONE scalar vector (ElGamal decryption under one key as `(1, -x)`, the Lagrange
+    /// coefficients of a threshold decryption, `(u^-1, u)` of a generator folding): the same group elements as `ed_lincomb`
+    /// with `k` in every row, on one schedule merged from the terms' recodings on the host.  The running time depends on `k`.
+    pub fn ed_lincomb_shared(&self, p: &[Vec<EdwardsPoint>], k: &[Scalar]) -> Result<Vec<EdwardsPoint>> {
+        let (n, t) = (p.len(), k.len());
+        assert!(p.iter().all(|row| row.len() == t), "one point per scalar in every row");
+        let fp: Vec<u64> = p.iter().flat_map(|row| flat_ed(row)).collect();
+        let fk = flat_sc(k);
+        let mut out = vec![0u64; n * 20];
+        if n > 0 {
+            check(unsafe { zc_ed_lincomb_shared(self.ctx, fp.as_ptr(), fk.as_ptr(), t, out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_ed(&out))
+    }
+
+    /// `(sum_j c[i][j].decompress()? * k[j]).compress()` for every row and ONE scalar vector, byte-identical to `ris_lincomb`
+    /// without a base term and with `k` in every row; `None` where a term does not decode.  No basepoint term: pass the
+    /// encoding of the basepoint as a term.
+    pub fn ris_lincomb_shared(&self, c: &[Vec<CompressedRistretto>], k: &[Scalar]) -> Result<Vec<Option<CompressedRistretto>>> {
+        let (n, t) = (c.len(), k.len());
+        assert!(c.iter().all(|row| row.len() == t), "one encoding per scalar in every row");
+        let flat: Vec<u8> = c.iter().flat_map(|row| row.iter().flat_map(|e| e.0.iter().copied())).collect();
+        let fk = flat_sc(k);
+        let (mut out, mut ok) = (vec![0u8; n * 32], vec![0u8; n]);
+        if n > 0 {
+            check(unsafe { zc_ris_lincomb_shared(self.ctx, flat.as_ptr(), fk.as_ptr(), t, out.as_mut_ptr(), ok.as_mut_ptr(), n) })?;
         }
         let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
         Ok(masked(enc, &ok))

@@ -1448,18 +1448,13 @@ ZC_DI pt lincomb_strict(const u64* __restrict__ points, const u64* __restrict__ 
 // that read the table); here so that the host-emulation tier drives the same functions.
 constexpr int ZC_BASE_WINDOWS = 33;                      // signed radix-256 digits of a 260-bit scalar (+ carry)
 constexpr int ZC_BASE_ENTRIES = 128;                     // |digit| = 1 .. 128
-// column j (0..127) of the table: (j+1) * 256^w * B for w = 0..32
-ZC_DI void base_table_column(u32* __restrict__ table, int j)
+// column j (0..127) of the comb of any point G: (j+1) * 256^w * G for w = 0..32 (zc_gens.hip.h builds one per generator)
+ZC_DI void comb_table_column(u32* __restrict__ table, const pt& G, int j)
 {
-    pt B;
-    B.X = fe_const<FP>(ModP::BASE_X_M);
-    B.Y = fe_const<FP>(ModP::BASE_Y_M);
-    B.Z = fe_one_m<FP>();
-    B.T = fe_const<FP>(ModP::BASE_T_M);
-    pt P = B;
+    pt P = G;
     for (int a = 0; a < ZC_BASE_ENTRIES - 1; a++) {
-        const pt s = pt_add(P, B);
-        P = pt_select(a < j, s, P);                       // P = (j+1) * B
+        const pt s = pt_add(P, G);
+        P = pt_select(a < j, s, P);                       // P = (j+1) * G
     }
     for (int w = 0; w < ZC_BASE_WINDOWS; w++) {
         // entries are normalised to Z = 1 once, here, so every later addition against them is mixed
@@ -1473,6 +1468,16 @@ ZC_DI void base_table_column(u32* __restrict__ table, int j)
 #pragma unroll 1
         for (int t = 0; t < 8; t++) P = pt_add(P, P);
     }
+}
+// the basepoint's column: the same words as before the builder took its point as an argument (tests/test_gens_emul.py)
+ZC_DI void base_table_column(u32* __restrict__ table, int j)
+{
+    pt B;
+    B.X = fe_const<FP>(ModP::BASE_X_M);
+    B.Y = fe_const<FP>(ModP::BASE_Y_M);
+    B.Z = fe_one_m<FP>();
+    B.T = fe_const<FP>(ModP::BASE_T_M);
+    comb_table_column(table, B, j);
 }
 // Signed radix-256 digits of the 260-bit scalar, d_i in [-128, 128), 33 digits (carry included), stored as
 // bytes at dig[i * stride]; returns the index of the highest non-zero digit or -1.

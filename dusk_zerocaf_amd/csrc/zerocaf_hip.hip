@@ -31,6 +31,7 @@
 #include "zc_ris_batch.hip.h"
 #include "zc_hash.hip.h"
 #include "zc_shared.hip.h"
+#include "zc_gens.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -293,12 +294,18 @@ struct MsmBases {
     int c = 0, W = 0;
 };
 std::atomic<uint64_t> g_next_bases_id{1};   // table ids: nonzero, process-wide, never reused
+// A generator set (zc_gens_create): `count` comb tables one behind the other, a copy on every device slot of the context.
+struct GenSet {
+    size_t count = 0;
+    std::vector<DevBuf> tables;             // by device slot
+};
 
 }  // namespace
 
 struct zc_ctx {
     std::map<uint64_t, MsmBases> bases;   // live fixed-base tables by id (ids come from one process-wide counter: never reused);
                                           // declared before the slots, so released after every slot has drained its streams
+    std::map<uint64_t, GenSet> gens;      // live generator sets by id, from the same counter; released after the slots too
     std::vector<DevState> devs;           // reserved at creation: the slots never move
     std::mutex mu;
     ncclComm_t comm = nullptr;          // zc_comm_init: one rank per process, device 0 of the context
@@ -1797,6 +1804,125 @@ int zc_ed_mul_base_wnaf(zc_ctx* ctx, const uint64_t* k, unsigned width, uint64_t
         hipLaunchKernelGGL(zc::k_ed_mul_base_wnaf, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, (zc::u32)width, dout, t, cnt);
         return ZC_OK;
     }, ROWS(k, 5), ROWS(out, 20));
+}
+
+// ---- generator sets (zerocaf_hip_ext_gens.h): the basepoint's comb over caller-supplied points (zc_gens.hip.h)
+// The tables of one device slot: the points uploaded, checked and normalised by the builder itself, which reports a generator
+// that is no curve point in `bad`.  Everything enqueued is through before the staging block goes.
+static int gens_build_on(DevState& D, const u64* host_points, size_t count, DevBuf& tables, int* first_bad)
+{
+    if (int rc = ring_check(D)) return rc;
+    HIP_TRY(hipSetDevice(D.device));
+    if (int rc = tables.alloc(count * zc::GENS_TABLE_WORDS * sizeof(zc::u32), "zc_gens_create: hipMalloc(tables)")) return rc;
+    DevBuf stage;                                           // the points, then one flag per generator
+    if (int rc = stage.alloc(count * 160 + count * sizeof(zc::u32), "zc_gens_create: hipMalloc(points)")) return rc;
+    u64* const dpts = stage.as<u64>();
+    zc::u32* const dbad = reinterpret_cast<zc::u32*>(dpts + 20 * count);
+    zc::u32 bad[ZC_GENS_MAX] = {};
+    hipError_t e = hipMemcpyAsync(dpts, host_points, count * 160, hipMemcpyHostToDevice, D.s());
+    if (e == hipSuccess) e = hipMemsetAsync(dbad, 0, count * sizeof(zc::u32), D.s());
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(zc::k_gens_table_build, dim3((unsigned)count), dim3(zc::ZC_BASE_ENTRIES), 0, D.s(), (const u64*)dpts, tables.as<zc::u32>(), dbad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(bad, dbad, count * sizeof(zc::u32), hipMemcpyDeviceToHost, D.s());
+    const hipError_t synced = hipStreamSynchronize(D.s());
+    if (e != hipSuccess || synced != hipSuccess) return fail(ZC_ERR_HIP, "zc_gens_create: table build", e != hipSuccess ? e : synced);
+    for (size_t j = count; j-- > 0;)
+        if (bad[j]) *first_bad = (int)j;
+    return ZC_OK;
+}
+int zc_gens_create(zc_ctx* ctx, const uint64_t* points, size_t count, uint64_t* id_out)
+{
+    REQUIRE(points);
+    REQUIRE(id_out);
+    if (count < 1 || count > ZC_GENS_MAX) return fail(ZC_ERR_BAD_ARG, "zc_gens_create: count must be 1 .. ZC_GENS_MAX");
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {points}, "zc_gens_create: ", &owner)) return rc;
+    u64 host[20 * ZC_GENS_MAX];                             // device-resident points come down once and go up to every slot
+    if (owner) {
+        HIP_TRY(hipSetDevice(owner->device));
+        HIP_TRY(hipMemcpyAsync(host, points, count * 160, hipMemcpyDeviceToHost, owner->s()));
+        HIP_TRY(hipStreamSynchronize(owner->s()));
+    } else {
+        memcpy(host, points, count * 160);
+    }
+    GenSet g;
+    g.count = count;
+    g.tables.resize(ctx->devs.size());
+    int first_bad = -1;
+    int rc = ZC_OK;
+    for (size_t di = 0; di < ctx->devs.size() && !rc && first_bad < 0; di++) rc = gens_build_on(ctx->devs[di], host, count, g.tables[di], &first_bad);
+    (void)hipSetDevice(ctx->devs[0].device);
+    if (rc) return rc;
+    if (first_bad >= 0) return failf(ZC_ERR_BAD_ARG, "zc_gens_create: generator %d is not a point of the curve", first_bad);
+    const uint64_t id = g_next_bases_id.fetch_add(1);
+    ctx->gens.emplace(id, std::move(g));
+    *id_out = id;
+    return ZC_OK;
+}
+int zc_gens_destroy(zc_ctx* ctx, uint64_t id)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    auto it = ctx->gens.find(id);
+    if (it == ctx->gens.end()) return fail(ZC_ERR_BAD_ARG, "unknown generator set");
+    for (DevState& D : ctx->devs) {                         // work that reads the tables ends before they go
+        HIP_TRY(hipSetDevice(D.device));
+        HIP_TRY(hipStreamSynchronize(D.s()));
+    }
+    (void)hipSetDevice(ctx->devs[0].device);
+    ctx->gens.erase(it);
+    return ZC_OK;
+}
+// The checks of the two row calls behind their pointers, in the header's order, and the set's term count.
+static int gens_row_args(zc_ctx* ctx, uint64_t id, size_t n, const char* who, size_t* count)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        auto it = ctx->gens.find(id);
+        if (it == ctx->gens.end()) return fail(ZC_ERR_BAD_ARG, "unknown generator set");
+        *count = it->second.count;
+    }
+    if (n >= ((size_t)1 << 31) / *count + (((size_t)1 << 31) % *count != 0)) return failf(ZC_ERR_BAD_ARG, "%s: n * count must stay below 2^31", who);
+    return ZC_OK;
+}
+// The set's tables on slot D, looked up again under the lock the batched call holds (a set destroyed in between is refused).
+static int gens_tables(zc_ctx* ctx, uint64_t id, DevState& D, const zc::u32** tables)
+{
+    auto it = ctx->gens.find(id);
+    if (it == ctx->gens.end()) return fail(ZC_ERR_BAD_ARG, "unknown generator set");
+    *tables = it->second.tables[(size_t)(&D - ctx->devs.data())].as<const zc::u32>();
+    return ZC_OK;
+}
+int zc_ed_mul_gens(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, uint64_t* out, size_t n)
+{
+    REQUIRE(scalars);
+    REQUIRE(out);
+    size_t count = 0;
+    if (int rc = gens_row_args(ctx, id, n, "zc_ed_mul_gens", &count)) return rc;
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, u64* dout) -> int {
+        const zc::u32* t = nullptr;
+        if (int rc = gens_tables(ctx, id, D, &t)) return rc;
+        hipLaunchKernelGGL(zc::k_ed_mul_gens, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, (zc::u32)count, cnt);
+        return ZC_OK;
+    }, ROWS(scalars, 5 * count), ROWS(out, 20));
+}
+int zc_ris_mul_gens_compress(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, uint8_t* out32, size_t n)
+{
+    REQUIRE(scalars);
+    REQUIRE(out32);
+    size_t count = 0;
+    if (int rc = gens_row_args(ctx, id, n, "zc_ris_mul_gens_compress", &count)) return rc;
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, uint8_t* dout) -> int {
+        const zc::u32* t = nullptr;
+        if (int rc = gens_tables(ctx, id, D, &t)) return rc;
+        hipLaunchKernelGGL(zc::k_ris_mul_gens_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, (zc::u32)count, cnt);
+        return ZC_OK;
+    }, ROWS(scalars, 5 * count), ROWS(out32, 32));
 }
 
 // ---- MSM: sum_i k_i * P_i (not in the reference; specified as the reference's own

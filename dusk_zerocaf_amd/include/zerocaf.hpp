@@ -942,6 +942,57 @@ inline std::vector<CompressedRistretto> ristretto_keygen_batch(const std::vector
     for (size_t i = 0; i < ks.size(); i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
     return out;
 }
+// A generator set (zc_gens_create, zerocaf_hip_ext_gens.h through zerocaf_hip_ext.h), freed when the object goes: 1..8 fixed points
+// of the caller's with a comb table each -- the second Pedersen generator, a recipient key, the bases of a DLEQ proof.  mul() and
+// mul_compress() are mul_base_batch and ristretto_keygen_batch over them: row i is ((kss[i][0]*G_0 + kss[i][1]*G_1) + ...) under ==.
+// A point that is not on the curve is refused (std::runtime_error from Backend::check).  Nothing is constant-time.
+class Generators {
+public:
+    explicit Generators(const std::vector<EdwardsPoint>& gs) : count_(gs.size())
+    {
+        std::vector<uint64_t> p(gs.size() * 20);
+        for (size_t j = 0; j < gs.size(); j++) gs[j].flat(&p[20 * j]);
+        Backend::check(zc_gens_create(Backend::ctx(), p.data(), gs.size(), &id_), "zc_gens_create");
+    }
+    Generators(const Generators&) = delete;
+    Generators& operator=(const Generators&) = delete;
+    Generators(Generators&& o) noexcept : id_(o.id_), count_(o.count_) { o.id_ = 0; }
+    ~Generators()
+    {
+        if (id_) zc_gens_destroy(Backend::ctx(), id_);
+    }
+    size_t size() const { return count_; }
+    std::vector<EdwardsPoint> mul(const std::vector<std::vector<Scalar>>& kss) const
+    {
+        std::vector<uint64_t> k = flat(kss), o(kss.size() * 20);
+        if (!kss.empty()) Backend::check(zc_ed_mul_gens(Backend::ctx(), id_, k.data(), o.data(), kss.size()), "zc_ed_mul_gens");
+        std::vector<EdwardsPoint> out(kss.size());
+        for (size_t i = 0; i < kss.size(); i++) out[i] = EdwardsPoint::unflat(&o[20 * i]);
+        return out;
+    }
+    std::vector<CompressedRistretto> mul_compress(const std::vector<std::vector<Scalar>>& kss) const
+    {
+        std::vector<uint64_t> k = flat(kss);
+        std::vector<uint8_t> o(kss.size() * 32);
+        if (!kss.empty()) Backend::check(zc_ris_mul_gens_compress(Backend::ctx(), id_, k.data(), o.data(), kss.size()), "zc_ris_mul_gens_compress");
+        std::vector<CompressedRistretto> out(kss.size());
+        for (size_t i = 0; i < kss.size(); i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
+        return out;
+    }
+
+private:
+    std::vector<uint64_t> flat(const std::vector<std::vector<Scalar>>& kss) const
+    {
+        std::vector<uint64_t> k(kss.size() * count_ * 5);
+        for (size_t i = 0; i < kss.size(); i++) {
+            if (kss[i].size() != count_) throw std::invalid_argument("Generators: a row without one scalar per generator");
+            for (size_t j = 0; j < count_; j++) std::memcpy(&k[5 * (i * count_ + j)], kss[i][j].l.data(), 40);
+        }
+        return k;
+    }
+    uint64_t id_ = 0;
+    size_t count_ = 0;
+};
 
 namespace constants {
 // src/backend/u64/constants.rs:188-211

@@ -1,6 +1,7 @@
 //! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h` / `zerocaf_hip_ext_hash.h`,
 //! which it includes).  The calls with one scalar for a whole batch (`zerocaf_hip_ext_shared.h`, included likewise) and with one
-//! scalar vector for a whole batch (`zerocaf_hip_ext_shared_lincomb.h`) are at the end.
+//! scalar vector for a whole batch (`zerocaf_hip_ext_shared_lincomb.h`) follow; the generator sets (`zerocaf_hip_ext_gens.h`) are
+//! at the end.
 //!
 //! `ffi.rs` is the rendering of `zerocaf_hip.h` and stays exactly that; calls declared in the second header are bound here,
 //! with their own `extern "C"` block and a safe wrapper each.
@@ -33,6 +34,14 @@ extern "C" {
     pub fn zc_ed_lincomb_shared(ctx: *mut ZcCtx, points: *const u64, k: *const u64, terms: usize, out: *mut u64, n: usize) -> c_int;
     /// `out32[i] = compress(sum_j k_j * decompress(in32[i][j]))` for ONE scalar vector `k`; see `zerocaf_hip_ext_shared_lincomb.h`.
     pub fn zc_ris_lincomb_shared(ctx: *mut ZcCtx, in32: *const u8, k: *const u64, terms: usize, out32: *mut u8, ok: *mut u8, n: usize) -> c_int;
+    /// A generator set of `count` = 1..8 points with a comb table each, on every device of the context; see `zerocaf_hip_ext_gens.h`.
+    pub fn zc_gens_create(ctx: *mut ZcCtx, points: *const u64, count: usize, id_out: *mut u64) -> c_int;
+    /// Frees the set after the context's streams have drained.
+    pub fn zc_gens_destroy(ctx: *mut ZcCtx, id: u64) -> c_int;
+    /// `out[i] = sum_j scalars[i][j] * G_j` over the set `id`: 33 mixed additions per term.
+    pub fn zc_ed_mul_gens(ctx: *mut ZcCtx, id: u64, scalars: *const u64, out: *mut u64, n: usize) -> c_int;
+    /// `out32[i]` = the Ristretto encoding of that sum.
+    pub fn zc_ris_mul_gens_compress(ctx: *mut ZcCtx, id: u64, scalars: *const u64, out32: *mut u8, n: usize) -> c_int;
 }
 
 /// The message arguments of the three SHA-512 calls from `parts[j]` = n rows of `part_len[j]` contiguous bytes: (pointers, lengths, n).
@@ -177,5 +186,46 @@ impl HipBackend {
         }
         let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
         Ok(masked(enc, &ok))
+    }
+
+    /// A generator set over `g` (1..8 points: the second Pedersen generator, a recipient key, the bases of a DLEQ proof): the
+    /// id `ed_mul_gens` and `ris_mul_gens_compress` take.  The tables are complete when this returns.  A point that is not on
+    /// the curve is refused.  Free the set with `gens_destroy`; the context frees the sets that are left.
+    pub fn gens_create(&self, g: &[EdwardsPoint]) -> Result<u64> {
+        let fp = flat_ed(g);
+        let mut id = 0u64;
+        check(unsafe { zc_gens_create(self.ctx, fp.as_ptr(), g.len(), &mut id) })?;
+        Ok(id)
+    }
+
+    /// Frees the generator set `id` once the work that reads its tables has finished.
+    pub fn gens_destroy(&self, id: u64) -> Result<()> {
+        check(unsafe { zc_gens_destroy(self.ctx, id) })
+    }
+
+    /// `sum_j k[i][j] * G_j` for every row over the set `id` of `count` generators: the same group elements as `&G_j * &k` and
+    /// `+` in index order -- equal under `==`, identical encodings, another projective representative.  Not constant-time.
+    pub fn ed_mul_gens(&self, id: u64, count: usize, k: &[Vec<Scalar>]) -> Result<Vec<EdwardsPoint>> {
+        assert!(k.iter().all(|row| row.len() == count), "one scalar per generator in every row");
+        let fk: Vec<u64> = k.iter().flat_map(|row| flat_sc(row)).collect();
+        let n = k.len();
+        let mut out = vec![0u64; n * 20];
+        if n > 0 {
+            check(unsafe { zc_ed_mul_gens(self.ctx, id, fk.as_ptr(), out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_ed(&out))
+    }
+
+    /// `RistrettoPoint(sum_j k[i][j] * G_j).compress()` for every row: a Pedersen commitment `v * G + r * H` as it goes on the
+    /// wire.  The bytes are those of the reference's composition; an identity sum is 32 zero bytes.
+    pub fn ris_mul_gens_compress(&self, id: u64, count: usize, k: &[Vec<Scalar>]) -> Result<Vec<CompressedRistretto>> {
+        assert!(k.iter().all(|row| row.len() == count), "one scalar per generator in every row");
+        let fk: Vec<u64> = k.iter().flat_map(|row| flat_sc(row)).collect();
+        let n = k.len();
+        let mut out = vec![0u8; n * 32];
+        if n > 0 {
+            check(unsafe { zc_ris_mul_gens_compress(self.ctx, id, fk.as_ptr(), out.as_mut_ptr(), n) })?;
+        }
+        Ok(out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect())
     }
 }

@@ -32,6 +32,7 @@
 #include "zc_hash.hip.h"
 #include "zc_shared.hip.h"
 #include "zc_gens.hip.h"
+#include "zc_sum.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -221,6 +222,7 @@ struct DevState {
     DevBuf bal;                         // lane balancing: 1024 u32 bins + n u32 indices
     DevBuf msm;                         // the MSM workspace: bucket method, or the products and folds of a small shard / batch
     DevBuf ris_sum;                     // zc_ris_lincomb_sum: the MSM inputs it prepares (records, scalars, flags, base-term partials)
+    DevBuf sum;                         // zc_ed_sum_rows / zc_ris_sum_rows: the partials between their two kernels (zc_sum_plan.h)
     DevBuf fast;                        // windowed-core tables: ring of wave slots, 256 MB (zc_kernels.hip.h)
     DevBuf ring;                        // tickets and slot flags of the table ring (+ the device address of the error word)
     PinnedMem ring_err;                 // the ring's error word: pinned host memory, written by a wave that gave up
@@ -1923,6 +1925,62 @@ int zc_ris_mul_gens_compress(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, 
         hipLaunchKernelGGL(zc::k_ris_mul_gens_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, (zc::u32)count, cnt);
         return ZC_OK;
     }, ROWS(scalars, 5 * count), ROWS(out32, 32));
+}
+
+// ---- point sums (zerocaf_hip_ext_sum_rows.h): out[i] = P_i0 + P_i1 + ... in the order zc_sum_plan.h fixes for `terms` (kernels:
+// zc_sum.hip.h).  The checks behind the pointers, in the header's order.
+static int sum_rows_args(zc_ctx* ctx, size_t n, size_t terms, const char* who)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (zc::sum_too_large(n, terms)) return failf(ZC_ERR_BAD_ARG, "%s: n * terms must stay below 2^31", who);
+    return ZC_OK;
+}
+// The launches of `cnt` rows on slot D: one kernel, or -- more slices than a workgroup has lanes -- the first kernel into the
+// slot's `sum` workspace and the one that finishes the rows, both on the slot's stream (a later call's kernels come behind them;
+// a workspace that has to grow is freed first, which waits for the device).
+}  // extern "C"
+template <class K1, class KP, class K2, class IN, class... OUT>
+static int sum_rows_launch(DevState& D, size_t cnt, size_t terms, K1 whole, KP part, K2 finish, const IN* in, OUT*... out)
+{
+    const zc::SumPlan p = zc::sum_plan(cnt, terms);
+    if (p.grid1 >= ((size_t)1 << 31)) return fail(ZC_ERR_BAD_ARG, "more rows than one launch holds");       // rows without terms only: n * terms < 2^31 bounds every other grid
+    if (p.form == zc::SUM_FORM_GROUP) {
+        hipLaunchKernelGGL(whole, dim3((unsigned)p.grid1), dim3(zc::SUM_BLOCK), 0, D.s(), in, (zc::u32)terms, (zc::u32)p.parts, out..., cnt);
+        return ZC_OK;
+    }
+    if (int rc = D.sum.grow(p.workspace_bytes)) return rc;
+    zc::u32* const ws = D.sum.as<zc::u32>();
+    hipLaunchKernelGGL(part, dim3((unsigned)p.grid1), dim3(zc::SUM_BLOCK), 0, D.s(), in, (zc::u32)terms, (zc::u32)p.parts, ws);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(finish, dim3((unsigned)p.grid2), dim3(zc::SUM_BLOCK), 0, D.s(), (const zc::u32*)ws, (zc::u32)p.blocks_per_row, out..., cnt);
+    return ZC_OK;
+}
+extern "C" {
+int zc_ed_sum_rows(zc_ctx* ctx, const uint64_t* points, size_t terms, uint64_t* out, size_t n)
+{
+    REQUIRE(points);
+    REQUIRE(out);
+    if (int rc = sum_rows_args(ctx, n, terms, "zc_ed_sum_rows")) return rc;
+    if (terms == 0)                                         // nothing of `points` is read: identity rows
+        return batched(ctx, n, false, [&](DevState& D, size_t cnt, u64* dout) -> int {
+            return sum_rows_launch(D, cnt, 0, zc::k_ed_rowsum, zc::k_ed_rowsum_part, zc::k_ed_rowsum_finish, (const u64*)nullptr, dout);
+        }, ROWS(out, 20));
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dp, u64* dout) -> int {
+        return sum_rows_launch(D, cnt, terms, zc::k_ed_rowsum, zc::k_ed_rowsum_part, zc::k_ed_rowsum_finish, dp, dout);
+    }, ROWS(points, 20 * terms), ROWS(out, 20));
+}
+int zc_ris_sum_rows(zc_ctx* ctx, const uint8_t* in32, size_t terms, uint8_t* out32, uint8_t* ok, size_t n)
+{
+    REQUIRE(in32);
+    REQUIRE(out32);
+    if (int rc = sum_rows_args(ctx, n, terms, "zc_ris_sum_rows")) return rc;
+    if (terms == 0)
+        return batched(ctx, n, false, [&](DevState& D, size_t cnt, uint8_t* dout, uint8_t* dok) -> int {
+            return sum_rows_launch(D, cnt, 0, zc::k_ris_rowsum, zc::k_ris_rowsum_part, zc::k_ris_rowsum_finish, (const uint8_t*)nullptr, dout, dok);
+        }, ROWS(out32, 32), OPT_ROWS(ok, 1));
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const uint8_t* din, uint8_t* dout, uint8_t* dok) -> int {
+        return sum_rows_launch(D, cnt, terms, zc::k_ris_rowsum, zc::k_ris_rowsum_part, zc::k_ris_rowsum_finish, din, dout, dok);
+    }, ROWS(in32, 32 * terms), ROWS(out32, 32), OPT_ROWS(ok, 1));
 }
 
 // ---- MSM: sum_i k_i * P_i (not in the reference; specified as the reference's own

@@ -993,6 +993,38 @@ private:
     uint64_t id_ = 0;
     size_t count_ = 0;
 };
+// Point sums (zc_ed_sum_rows / zc_ris_sum_rows, zerocaf_hip_ext_sum_rows.h through zerocaf_hip_ext.h): row i is rows[i][0] + rows[i][1] + ...
+// under the unified addition, associated in the order the header fixes for the row length (a left fold up to 32 terms, strided
+// slices and a pairwise tree above) -- an ElGamal tally, an aggregate of keys or commitments.  Every row has the same length
+// (pad with EdwardsPoint::identity() / the zero encoding); empty rows give the identity.
+inline std::vector<EdwardsPoint> sum_rows(const std::vector<std::vector<EdwardsPoint>>& rows)
+{
+    const size_t n = rows.size(), terms = n ? rows[0].size() : 0;
+    std::vector<uint64_t> p(n * terms * 20 + 20), o(n * 20);
+    for (size_t i = 0; i < n; i++) {
+        if (rows[i].size() != terms) throw std::invalid_argument("sum_rows: rows of different lengths");
+        for (size_t j = 0; j < terms; j++) rows[i][j].flat(&p[20 * (i * terms + j)]);
+    }
+    if (n) Backend::check(zc_ed_sum_rows(Backend::ctx(), p.data(), terms, o.data(), n), "zc_ed_sum_rows");
+    std::vector<EdwardsPoint> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = EdwardsPoint::unflat(&o[20 * i]);
+    return out;
+}
+// The same between the Ristretto codecs: compress(sum_j decompress(rows[i][j])); ok[i] = 0 (and 32 zero bytes) where a term does not decode.
+inline std::vector<CompressedRistretto> sum_rows(const std::vector<std::vector<CompressedRistretto>>& rows, std::vector<uint8_t>* ok = nullptr)
+{
+    const size_t n = rows.size(), terms = n ? rows[0].size() : 0;
+    std::vector<uint8_t> in(n * terms * 32 + 32), o(n * 32), accept(n);
+    for (size_t i = 0; i < n; i++) {
+        if (rows[i].size() != terms) throw std::invalid_argument("sum_rows: rows of different lengths");
+        for (size_t j = 0; j < terms; j++) std::memcpy(&in[32 * (i * terms + j)], rows[i][j].bytes.data(), 32);
+    }
+    if (n) Backend::check(zc_ris_sum_rows(Backend::ctx(), in.data(), terms, o.data(), accept.data(), n), "zc_ris_sum_rows");
+    std::vector<CompressedRistretto> out(n);
+    for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
+    if (ok) *ok = accept;
+    return out;
+}
 
 namespace constants {
 // src/backend/u64/constants.rs:188-211

@@ -44,5 +44,6 @@ int zc_ris_double_and_compress(zc_ctx *ctx, const uint64_t *p, uint8_t *out32, s
 #include "zerocaf_hip_ext_shared.h"
 #include "zerocaf_hip_ext_shared_lincomb.h"
 #include "zerocaf_hip_ext_gens.h"
+#include "zerocaf_hip_ext_sum_rows.h"
 
 #endif /* ZEROCAF_HIP_EXT_H */

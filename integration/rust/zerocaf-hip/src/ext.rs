@@ -42,6 +42,10 @@ extern "C" {
     pub fn zc_ed_mul_gens(ctx: *mut ZcCtx, id: u64, scalars: *const u64, out: *mut u64, n: usize) -> c_int;
     /// `out32[i]` = the Ristretto encoding of that sum.
     pub fn zc_ris_mul_gens_compress(ctx: *mut ZcCtx, id: u64, scalars: *const u64, out32: *mut u8, n: usize) -> c_int;
+    /// `out[i] = points[i][0] + points[i][1] + ...` over rows of `terms` points; see `zerocaf_hip_ext_sum_rows.h`.
+    pub fn zc_ed_sum_rows(ctx: *mut ZcCtx, points: *const u64, terms: usize, out: *mut u64, n: usize) -> c_int;
+    /// `out32[i] = compress(sum_j decompress(in32[i][j]))`; `ok` may be null.
+    pub fn zc_ris_sum_rows(ctx: *mut ZcCtx, in32: *const u8, terms: usize, out32: *mut u8, ok: *mut u8, n: usize) -> c_int;
 }
 
 /// The message arguments of the three SHA-512 calls from `parts[j]` = n rows of `part_len[j]` contiguous bytes: (pointers, lengths, n).
@@ -227,5 +231,36 @@ impl HipBackend {
             check(unsafe { zc_ris_mul_gens_compress(self.ctx, id, fk.as_ptr(), out.as_mut_ptr(), n) })?;
         }
         Ok(out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect())
+    }
+
+    /// `p[i][0] + p[i][1] + ...` for every row (`zerocaf_hip_ext_sum_rows.h`): rows of one length, any length -- a tally, an
+    /// aggregate of keys or commitments.  The additions are the reference's, associated in the order the header fixes for the
+    /// row length (a left fold up to 32 terms; strided slices and a pairwise tree above).  Empty rows give the identity.
+    pub fn ed_sum_rows(&self, p: &[Vec<EdwardsPoint>]) -> Result<Vec<EdwardsPoint>> {
+        let n = p.len();
+        let t = p.first().map_or(0, |row| row.len());
+        assert!(p.iter().all(|row| row.len() == t), "rows of one length");
+        let mut fp: Vec<u64> = p.iter().flat_map(|row| flat_ed(row)).collect();
+        fp.resize(fp.len().max(20), 0);                     // a non-null pointer for rows without terms
+        let mut out = vec![0u64; n * 20];
+        if n > 0 {
+            check(unsafe { zc_ed_sum_rows(self.ctx, fp.as_ptr(), t, out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_ed(&out))
+    }
+
+    /// `(sum_j c[i][j].decompress()?).compress()` for every row; `None` where a term does not decode.
+    pub fn ris_sum_rows(&self, c: &[Vec<CompressedRistretto>]) -> Result<Vec<Option<CompressedRistretto>>> {
+        let n = c.len();
+        let t = c.first().map_or(0, |row| row.len());
+        assert!(c.iter().all(|row| row.len() == t), "rows of one length");
+        let mut flat: Vec<u8> = c.iter().flat_map(|row| row.iter().flat_map(|e| e.0.iter().copied())).collect();
+        flat.resize(flat.len().max(32), 0);
+        let (mut out, mut ok) = (vec![0u8; n * 32], vec![0u8; n]);
+        if n > 0 {
+            check(unsafe { zc_ris_sum_rows(self.ctx, flat.as_ptr(), t, out.as_mut_ptr(), ok.as_mut_ptr(), n) })?;
+        }
+        let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
+        Ok(masked(enc, &ok))
     }
 }

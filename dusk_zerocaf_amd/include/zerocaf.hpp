@@ -557,6 +557,7 @@ inline RistrettoPoint operator*(const Scalar& k, const RistrettoPoint& p) { retu
 inline std::vector<EdwardsPoint> mul_batch(const std::vector<EdwardsPoint>& ps, const std::vector<Scalar>& ks)
 {
     if (ps.size() != ks.size()) throw std::invalid_argument("mul_batch: size mismatch");
+    if (ps.empty()) return {};                                              // (data() of an empty vector is null, which the library refuses)
     std::vector<uint64_t> p(ps.size() * 20), k(ks.size() * 5), o(ps.size() * 20);
     for (size_t i = 0; i < ps.size(); i++) {
         ps[i].flat(&p[20 * i]);
@@ -570,6 +571,7 @@ inline std::vector<EdwardsPoint> mul_batch(const std::vector<EdwardsPoint>& ps, 
 inline std::vector<FieldElement> mul_batch(const std::vector<FieldElement>& a, const std::vector<FieldElement>& b)
 {
     if (a.size() != b.size()) throw std::invalid_argument("mul_batch: size mismatch");
+    if (a.empty()) return {};
     std::vector<uint64_t> x(a.size() * 5), y(a.size() * 5), o(a.size() * 5);
     for (size_t i = 0; i < a.size(); i++) {
         std::memcpy(&x[5 * i], a[i].l.data(), 40);
@@ -584,6 +586,7 @@ inline std::vector<std::optional<CompressedRistretto>> ristretto_roundtrip_mul_b
     const std::vector<CompressedRistretto>& enc, const std::vector<Scalar>& ks)
 {
     if (enc.size() != ks.size()) throw std::invalid_argument("size mismatch");
+    if (enc.empty()) return {};
     std::vector<uint8_t> in(enc.size() * 32), out(enc.size() * 32), ok(enc.size());
     std::vector<uint64_t> k(ks.size() * 5);
     for (size_t i = 0; i < enc.size(); i++) {
@@ -605,7 +608,7 @@ inline std::vector<std::optional<CompressedRistretto>> ristretto_roundtrip_mul_b
 inline EdwardsPoint msm(const std::vector<EdwardsPoint>& ps, const std::vector<Scalar>& ks)
 {
     if (ps.size() != ks.size()) throw std::invalid_argument("msm: size mismatch");
-    std::vector<uint64_t> p(ps.size() * 20), k(ks.size() * 5);
+    std::vector<uint64_t> p(ps.size() * 20 + 1), k(ks.size() * 5 + 1);      // (one spare element: data() is never null, and n == 0 is the empty sum)
     for (size_t i = 0; i < ps.size(); i++) {
         ps[i].flat(&p[20 * i]);
         std::memcpy(&k[5 * i], ks[i].l.data(), 40);
@@ -617,7 +620,7 @@ inline EdwardsPoint msm(const std::vector<EdwardsPoint>& ps, const std::vector<S
 // the exchange step of a sharded MSM: ((p_0 + p_1) + p_2) + ... in index order, one kernel launch
 inline EdwardsPoint fold_ordered(const std::vector<EdwardsPoint>& ps)
 {
-    std::vector<uint64_t> p(ps.size() * 20);
+    std::vector<uint64_t> p(ps.size() * 20 + 1);                            // (one spare element: an empty list is the library's to refuse)
     for (size_t i = 0; i < ps.size(); i++) ps[i].flat(&p[20 * i]);
     uint64_t o[20];
     Backend::check(zc_ed_fold_ordered(Backend::ctx(), p.data(), ps.size(), o), "zc_ed_fold_ordered");
@@ -640,7 +643,6 @@ inline void msm_partial(const uint64_t* points, const uint64_t* scalars, size_t 
 {
     Backend::check(zc_msm_partial(Backend::ctx(), points, scalars, n, out_dev), "zc_msm_partial");
 }
-// k * BASEPOINT from the fixed-base table: equal to `BASEPOINT * k` under == (not limb-identical)
 // the encodings of 2 * P_i without a square root: the rows share inversions (zerocaf_hip_ext.h).  compress(k * P) for a point of
 // order L is this call on (k * 2^-1 mod L) * P; a point of E[8] gives 32 zero bytes, as the reference's composition does
 inline std::vector<CompressedRistretto> double_and_compress_batch(const std::vector<RistrettoPoint>& ps)
@@ -653,8 +655,10 @@ inline std::vector<CompressedRistretto> double_and_compress_batch(const std::vec
     for (size_t i = 0; i < ps.size(); i++) std::memcpy(out[i].bytes.data(), &o[32 * i], 32);
     return out;
 }
+// k * BASEPOINT from the fixed-base table: equal to `BASEPOINT * k` under == (not limb-identical)
 inline std::vector<EdwardsPoint> mul_base_batch(const std::vector<Scalar>& ks)
 {
+    if (ks.empty()) return {};                                              // (data() of an empty vector is null, which the library refuses)
     std::vector<uint64_t> k(ks.size() * 5), o(ks.size() * 20);
     for (size_t i = 0; i < ks.size(); i++) std::memcpy(&k[5 * i], ks[i].l.data(), 40);
     Backend::check(zc_ed_mul_base(Backend::ctx(), k.data(), o.data(), ks.size()), "zc_ed_mul_base");
@@ -665,6 +669,7 @@ inline std::vector<EdwardsPoint> mul_base_batch(const std::vector<Scalar>& ks)
 // window_naf_mul (src/edwards.rs:155-171) with its table indexed correctly, one launch; width 2..7
 inline std::vector<EdwardsPoint> window_naf_mul_batch(const std::vector<Scalar>& ks, unsigned width)
 {
+    if (ks.empty()) return {};
     std::vector<uint64_t> k(ks.size() * 5), o(ks.size() * 20);
     for (size_t i = 0; i < ks.size(); i++) std::memcpy(&k[5 * i], ks[i].l.data(), 40);
     Backend::check(zc_ed_mul_base_wnaf(Backend::ctx(), k.data(), width, o.data(), ks.size()), "zc_ed_mul_base_wnaf");
@@ -686,7 +691,7 @@ inline std::vector<EdwardsPoint> msm_batch(const std::vector<std::vector<Edwards
 {
     if (pss.size() != kss.size()) throw std::invalid_argument("msm_batch: size mismatch");
     const size_t batch = pss.size(), n = batch ? pss[0].size() : 0;
-    std::vector<uint64_t> p(batch * n * 20), k(batch * n * 5), o(batch * 20);
+    std::vector<uint64_t> p(batch * n * 20 + 1), k(batch * n * 5 + 1), o(batch * 20);      // (one spare element: instances of no pairs are identities)
     for (size_t b = 0; b < batch; b++) {
         if (pss[b].size() != n || kss[b].size() != n) throw std::invalid_argument("msm_batch: instances of different lengths");
         for (size_t i = 0; i < n; i++) {
@@ -934,6 +939,7 @@ private:
 // key generation: (RISTRETTO_BASEPOINT * k).compress(), identical bytes
 inline std::vector<CompressedRistretto> ristretto_keygen_batch(const std::vector<Scalar>& ks)
 {
+    if (ks.empty()) return {};
     std::vector<uint64_t> k(ks.size() * 5);
     std::vector<uint8_t> o(ks.size() * 32);
     for (size_t i = 0; i < ks.size(); i++) std::memcpy(&k[5 * i], ks[i].l.data(), 40);
@@ -957,10 +963,17 @@ public:
     Generators(const Generators&) = delete;
     Generators& operator=(const Generators&) = delete;
     Generators(Generators&& o) noexcept : id_(o.id_), count_(o.count_) { o.id_ = 0; }
-    ~Generators()
+    Generators& operator=(Generators&& o) noexcept
     {
-        if (id_) zc_gens_destroy(Backend::ctx(), id_);
+        if (this != &o) {
+            reset();
+            id_ = o.id_;
+            count_ = o.count_;
+            o.id_ = 0;
+        }
+        return *this;
     }
+    ~Generators() { reset(); }
     size_t size() const { return count_; }
     std::vector<EdwardsPoint> mul(const std::vector<std::vector<Scalar>>& kss) const
     {
@@ -981,6 +994,11 @@ public:
     }
 
 private:
+    void reset()
+    {
+        if (id_) zc_gens_destroy(Backend::ctx(), id_);
+        id_ = 0;
+    }
     std::vector<uint64_t> flat(const std::vector<std::vector<Scalar>>& kss) const
     {
         std::vector<uint64_t> k(kss.size() * count_ * 5);

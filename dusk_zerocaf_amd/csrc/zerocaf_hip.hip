@@ -26,6 +26,7 @@
 
 #include "../../include/zerocaf_hip.h"
 #include "../../include/zerocaf_hip_ext.h"
+#include "../../include/zerocaf_hip_dlog.h"
 #include "zc_kernels.hip.h"
 #include "zc_msm.hip.h"
 #include "zc_ris_batch.hip.h"
@@ -33,6 +34,7 @@
 #include "zc_shared.hip.h"
 #include "zc_gens.hip.h"
 #include "zc_sum.hip.h"
+#include "zc_dlog.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -301,6 +303,13 @@ struct GenSet {
     size_t count = 0;
     std::vector<DevBuf> tables;             // by device slot
 };
+// A baby-step table (zc_dlog_create): per device slot the 2^t records and, behind them, the 2^(t+1) hash slots; the setup block
+// (stride point and launch offsets, zc_dlog_plan.h) stays on the host and travels in kernel arguments.
+struct DlogTable {
+    unsigned t = 0, flags = 0;
+    std::vector<zc::u32> setup;
+    std::vector<DevBuf> mem;                // by device slot
+};
 
 }  // namespace
 
@@ -308,6 +317,7 @@ struct zc_ctx {
     std::map<uint64_t, MsmBases> bases;   // live fixed-base tables by id (ids come from one process-wide counter: never reused);
                                           // declared before the slots, so released after every slot has drained its streams
     std::map<uint64_t, GenSet> gens;      // live generator sets by id, from the same counter; released after the slots too
+    std::map<uint64_t, DlogTable> dlogs;  // live baby-step tables by id, from the same counter; released after the slots too
     std::vector<DevState> devs;           // reserved at creation: the slots never move
     std::mutex mu;
     ncclComm_t comm = nullptr;          // zc_comm_init: one rank per process, device 0 of the context
@@ -1981,6 +1991,171 @@ int zc_ris_sum_rows(zc_ctx* ctx, const uint8_t* in32, size_t terms, uint8_t* out
     return batched(ctx, n, false, [&](DevState& D, size_t cnt, const uint8_t* din, uint8_t* dout, uint8_t* dok) -> int {
         return sum_rows_launch(D, cnt, terms, zc::k_ris_rowsum, zc::k_ris_rowsum_part, zc::k_ris_rowsum_finish, din, dout, dok);
     }, ROWS(in32, 32 * terms), ROWS(out32, 32), OPT_ROWS(ok, 1));
+}
+
+// ---- bounded discrete logs (zerocaf_hip_dlog.h): baby steps from a table, giant steps per row (kernels: zc_dlog.hip.h; sizes,
+// slices and the slot array: zc_dlog_plan.h)
+// Slot 0's share of zc_dlog_create: the setup block and the records, computed there and brought to the host.
+static int dlog_compute_on(DevState& D, const u64* host_point, DlogTable& tb, std::vector<u64>& records)
+{
+    if (int rc = ring_check(D)) return rc;
+    HIP_TRY(hipSetDevice(D.device));
+    DevBuf stage;                                           // the point, then the setup block
+    if (int rc = stage.alloc(160 + zc::DLOG_SETUP_WORDS * sizeof(zc::u32), "zc_dlog_create: hipMalloc(setup)")) return rc;
+    u64* const dpoint = stage.as<u64>();
+    zc::u32* const dsetup = reinterpret_cast<zc::u32*>(dpoint + 20);
+    tb.setup.assign(zc::DLOG_SETUP_WORDS, 0);
+    hipError_t e = hipMemcpyAsync(dpoint, host_point, 160, hipMemcpyHostToDevice, D.s());
+    if (e == hipSuccess) e = hipMemsetAsync(dsetup, 0, zc::DLOG_SETUP_WORDS * sizeof(zc::u32), D.s());
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(zc::k_dlog_setup, dim3(1), dim3(zc::DLOG_BLOCK), 0, D.s(), (const u64*)dpoint, dsetup, (zc::u32)tb.t, (zc::u32)tb.flags);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(tb.setup.data(), dsetup, zc::DLOG_SETUP_WORDS * sizeof(zc::u32), hipMemcpyDeviceToHost, D.s());
+    hipError_t synced = hipStreamSynchronize(D.s());
+    if (e != hipSuccess || synced != hipSuccess) return fail(ZC_ERR_HIP, "zc_dlog_create: setup", e != hipSuccess ? e : synced);
+    if (tb.setup[0] == zc::DLOG_SETUP_NOT_A_POINT) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: not a point of the curve");
+    if (tb.setup[0] != zc::DLOG_SETUP_OK) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: generator lies in E[8]");
+    if (int rc = tb.mem[0].alloc(zc::dlog_table_bytes(tb.t), "zc_dlog_create: hipMalloc(table)")) return rc;
+    records.resize(4 * zc::dlog_records(tb.t));
+    const size_t lanes = zc::dlog_build_lanes(tb.t);
+    hipLaunchKernelGGL(zc::k_dlog_records, dim3((unsigned)((lanes + zc::DLOG_BLOCK - 1) / zc::DLOG_BLOCK)), dim3(zc::DLOG_BLOCK), 0, D.s(), (const zc::u32*)dsetup,
+                       tb.mem[0].as<u64>(), (zc::u32)tb.t);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(records.data(), tb.mem[0].as<u64>(), zc::dlog_record_bytes(tb.t), hipMemcpyDeviceToHost, D.s());
+    synced = hipStreamSynchronize(D.s());
+    if (e != hipSuccess || synced != hipSuccess) return fail(ZC_ERR_HIP, "zc_dlog_create: records", e != hipSuccess ? e : synced);
+    return ZC_OK;
+}
+int zc_dlog_create(zc_ctx* ctx, const uint64_t* point, unsigned table_bits, unsigned flags, uint64_t* id_out)
+{
+    REQUIRE(point);
+    REQUIRE(id_out);
+    if (!zc::dlog_bits_ok(table_bits)) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: table_bits must be ZC_DLOG_MIN_BITS .. ZC_DLOG_MAX_BITS");
+    if (flags & ~ZC_DLOG_COSET4) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: unknown flag bits");
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {point}, "zc_dlog_create: ", &owner)) return rc;
+    u64 host[20];                                           // a device-resident point comes down once
+    if (owner) {
+        HIP_TRY(hipSetDevice(owner->device));
+        HIP_TRY(hipMemcpyAsync(host, point, 160, hipMemcpyDeviceToHost, owner->s()));
+        HIP_TRY(hipStreamSynchronize(owner->s()));
+    } else {
+        memcpy(host, point, 160);
+    }
+    DlogTable tb;
+    tb.t = table_bits;
+    tb.flags = flags;
+    tb.mem.resize(ctx->devs.size());
+    std::vector<u64> records, slots;
+    int rc = dlog_compute_on(ctx->devs[0], host, tb, records);
+    if (!rc) {
+        slots.resize(zc::dlog_slots(tb.t));
+        if (zc::dlog_build_slots(slots.data(), tb.t, records.data()) >= 0) rc = fail(ZC_ERR_BAD_ARG, "zc_dlog_create: two table entries coincide");
+    }
+    // the slots behind the records on every device slot; the records too where they were not computed
+    for (size_t di = 0; di < ctx->devs.size() && !rc; di++) {
+        DevState& D = ctx->devs[di];
+        if (di) rc = ring_check(D);
+        if (rc) break;
+        hipError_t e = hipSetDevice(D.device);
+        if (e == hipSuccess && di) {
+            rc = tb.mem[di].alloc(zc::dlog_table_bytes(tb.t), "zc_dlog_create: hipMalloc(table)");
+            if (rc) break;
+            e = hipMemcpyAsync(tb.mem[di].as<u64>(), records.data(), zc::dlog_record_bytes(tb.t), hipMemcpyHostToDevice, D.s());
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(tb.mem[di].as<u64>() + 4 * zc::dlog_records(tb.t), slots.data(), zc::dlog_slot_bytes(tb.t), hipMemcpyHostToDevice, D.s());
+        const hipError_t synced = hipStreamSynchronize(D.s());
+        if (e != hipSuccess || synced != hipSuccess) rc = fail(ZC_ERR_HIP, "zc_dlog_create: table upload", e != hipSuccess ? e : synced);
+    }
+    (void)hipSetDevice(ctx->devs[0].device);
+    if (rc) return rc;
+    const uint64_t id = g_next_bases_id.fetch_add(1);
+    ctx->dlogs.emplace(id, std::move(tb));
+    *id_out = id;
+    return ZC_OK;
+}
+int zc_dlog_destroy(zc_ctx* ctx, uint64_t id)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    auto it = ctx->dlogs.find(id);
+    if (it == ctx->dlogs.end()) return fail(ZC_ERR_BAD_ARG, "unknown dlog table");
+    for (DevState& D : ctx->devs) {                         // work that reads the table ends before it goes
+        HIP_TRY(hipSetDevice(D.device));
+        HIP_TRY(hipStreamSynchronize(D.s()));
+    }
+    (void)hipSetDevice(ctx->devs[0].device);
+    ctx->dlogs.erase(it);
+    return ZC_OK;
+}
+// The checks of the two row calls behind their pointers, in the header's order.
+static int dlog_row_args(zc_ctx* ctx, uint64_t id, uint64_t bound, size_t n, bool wire, const char* who)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    unsigned t = 0, flags = 0;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        auto it = ctx->dlogs.find(id);
+        if (it == ctx->dlogs.end()) return fail(ZC_ERR_BAD_ARG, "unknown dlog table");
+        t = it->second.t;
+        flags = it->second.flags;
+    }
+    if (wire && !(flags & ZC_DLOG_COSET4)) return fail(ZC_ERR_BAD_ARG, "zc_ris_dlog needs a ZC_DLOG_COSET4 table");
+    if (!zc::dlog_bound_ok(bound, t)) return failf(ZC_ERR_BAD_ARG, "%s: bound must be 1 .. 2^table_bits * ZC_DLOG_MAX_STEPS", who);
+    if (n >= ((size_t)1 << 31)) return failf(ZC_ERR_BAD_ARG, "%s: n must stay below 2^31", who);
+    return ZC_OK;
+}
+// The launches of `cnt` rows on slot D, all on its stream: the slices of zc_dlog_plan.h, launch k from the offset W_k.  The table
+// is looked up again under the lock the batched call holds (a table destroyed in between is refused).
+}  // extern "C"
+template <class K, class IN>
+static int dlog_launches_on(zc_ctx* ctx, uint64_t id, DevState& D, K kernel, const IN* in, uint64_t bound, u64* m_out, uint8_t* found, uint8_t* ok, size_t cnt)
+{
+    auto it = ctx->dlogs.find(id);
+    if (it == ctx->dlogs.end()) return fail(ZC_ERR_BAD_ARG, "unknown dlog table");
+    const DlogTable& tb = it->second;
+    const u64* const records = tb.mem[(size_t)(&D - ctx->devs.data())].as<const u64>();
+    zc::dlog_launch A;
+    A.table = zc::dlog_table{records, records + 4 * zc::dlog_records(tb.t), (zc::u32)tb.t};
+    A.coset4 = (tb.flags & ZC_DLOG_COSET4) ? 1u : 0u;
+    A.bound = bound;
+    static_assert(sizeof(zc::dlog_step) == 27 * sizeof(zc::u32), "a cached affine point is 27 consecutive words of the setup block");
+    memcpy(&A.S, tb.setup.data() + zc::DLOG_SETUP_STRIDE * zc::DLOG_SETUP_S, sizeof A.S);
+    const unsigned grid = (unsigned)((cnt + zc::DLOG_BLOCK - 1) / zc::DLOG_BLOCK);
+    for (uint64_t k = 0; k < zc::dlog_launches(bound, tb.t); k++) {
+        const zc::DlogSlice s = zc::dlog_slice(bound, tb.t, k);
+        A.launch = (zc::u32)k;
+        A.first = s.first;
+        A.chunks = s.chunks;
+        memcpy(&A.W, tb.setup.data() + zc::dlog_offset_word(k), sizeof A.W);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(zc::DLOG_BLOCK), 0, D.s(), in, m_out, found, ok, A, cnt);
+        HIP_TRY(hipGetLastError());
+    }
+    return ZC_OK;
+}
+extern "C" {
+int zc_ed_dlog(zc_ctx* ctx, uint64_t id, const uint64_t* p, uint64_t bound, uint64_t* m_out, uint8_t* found, uint8_t* ok, size_t n)
+{
+    REQUIRE(p);
+    REQUIRE(m_out);
+    REQUIRE(found);
+    if (int rc = dlog_row_args(ctx, id, bound, n, false, "zc_ed_dlog")) return rc;
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const u64* dp, u64* dm, uint8_t* df, uint8_t* dok) -> int {
+        return dlog_launches_on(ctx, id, D, zc::k_ed_dlog, dp, bound, dm, df, dok, cnt);
+    }, ROWS(p, 20), ROWS(m_out, 1), ROWS(found, 1), OPT_ROWS(ok, 1));
+}
+int zc_ris_dlog(zc_ctx* ctx, uint64_t id, const uint8_t* in32, uint64_t bound, uint64_t* m_out, uint8_t* found, uint8_t* ok, size_t n)
+{
+    REQUIRE(in32);
+    REQUIRE(m_out);
+    REQUIRE(found);
+    if (int rc = dlog_row_args(ctx, id, bound, n, true, "zc_ris_dlog")) return rc;
+    return batched(ctx, n, true, [&](DevState& D, size_t cnt, const uint8_t* din, u64* dm, uint8_t* df, uint8_t* dok) -> int {
+        return dlog_launches_on(ctx, id, D, zc::k_ris_dlog, din, bound, dm, df, dok, cnt);
+    }, ROWS(in32, 32), ROWS(m_out, 1), ROWS(found, 1), OPT_ROWS(ok, 1));
 }
 
 // ---- MSM: sum_i k_i * P_i (not in the reference; specified as the reference's own

@@ -16,6 +16,7 @@ import threading
 import numpy as np
 
 from . import _lib
+from .dlog import DlogMixin
 from .generators import GeneratorsMixin
 from .hash_batch import HashMixin
 from .point_sums import PointSumsMixin
@@ -47,7 +48,7 @@ def _one_call(method):
     return locked
 
 
-class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin, SharedScalarMixin, GeneratorsMixin, PointSumsMixin):
+class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin, SharedScalarMixin, GeneratorsMixin, PointSumsMixin, DlogMixin):
     """One zc_ctx.  `devices=None` = one slot on torch's current device when torch is loaded and sees a GPU; otherwise
     zc_ctx_create(NULL, 0): the calling thread's current HIP device (whatever hipSetDevice chose), read back from the
     context.  The context reads the library's tuning knobs (ZC_* environment variables)

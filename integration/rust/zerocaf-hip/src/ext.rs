@@ -1,7 +1,7 @@
 //! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h` / `zerocaf_hip_ext_hash.h`,
 //! which it includes).  The calls with one scalar for a whole batch (`zerocaf_hip_ext_shared.h`, included likewise) and with one
 //! scalar vector for a whole batch (`zerocaf_hip_ext_shared_lincomb.h`) follow; the generator sets (`zerocaf_hip_ext_gens.h`) are
-//! at the end.
+//! at the end, before the bounded discrete logs, which have a header of their own (`zerocaf_hip_dlog.h`).
 //!
 //! `ffi.rs` is the rendering of `zerocaf_hip.h` and stays exactly that; calls declared in the second header are bound here,
 //! with their own `extern "C"` block and a safe wrapper each.
@@ -262,5 +262,60 @@ impl HipBackend {
         }
         let enc: Vec<CompressedRistretto> = out.chunks_exact(32).map(|b| CompressedRistretto(bytes32(b))).collect();
         Ok(masked(enc, &ok))
+    }
+}
+
+// ---- bounded discrete logs (`include/zerocaf_hip_dlog.h`, a header beside `zerocaf_hip.h`): m with P = m * G, 0 <= m < bound
+extern "C" {
+    /// The baby-step table of the 2^`table_bits` multiples of `point` (of four times it with `ZC_DLOG_COSET4`), on every device of the context.
+    pub fn zc_dlog_create(ctx: *mut ZcCtx, point: *const u64, table_bits: u32, flags: u32, id_out: *mut u64) -> c_int;
+    /// Frees the table after the context's streams have drained.
+    pub fn zc_dlog_destroy(ctx: *mut ZcCtx, id: u64) -> c_int;
+    /// `found[i] = 1`, `m_out[i] = m` iff `p[i] == m * G` with `m < bound`; `ok` may be null.
+    pub fn zc_ed_dlog(ctx: *mut ZcCtx, id: u64, p: *const u64, bound: u64, m_out: *mut u64, found: *mut u8, ok: *mut u8, n: usize) -> c_int;
+    /// The same from Ristretto encodings (a `ZC_DLOG_COSET4` table); `ok[i] = 0` where a row does not decode.
+    pub fn zc_ris_dlog(ctx: *mut ZcCtx, id: u64, in32: *const u8, bound: u64, m_out: *mut u64, found: *mut u8, ok: *mut u8, n: usize) -> c_int;
+}
+
+/// `flags` of `dlog_create`: the table of 4 G, equality modulo E[4] -- Ristretto equality.
+pub const ZC_DLOG_COSET4: u32 = 1;
+
+impl HipBackend {
+    /// Builds the baby-step table of `g` with 2^`table_bits` records (`table_bits` = 4..22) and returns the id `ed_dlog` and
+    /// `ris_dlog` take.  A point that is not on the curve or lies in E[8] is refused.  Free the table with `dlog_destroy`; the
+    /// context frees the tables that are left.
+    pub fn dlog_create(&self, g: &EdwardsPoint, table_bits: u32, coset4: bool) -> Result<u64> {
+        let fp = flat_ed(std::slice::from_ref(g));
+        let mut id = 0u64;
+        check(unsafe { zc_dlog_create(self.ctx, fp.as_ptr(), table_bits, if coset4 { ZC_DLOG_COSET4 } else { 0 }, &mut id) })?;
+        Ok(id)
+    }
+
+    /// Frees the table `id`.
+    pub fn dlog_destroy(&self, id: u64) -> Result<()> {
+        check(unsafe { zc_dlog_destroy(self.ctx, id) })
+    }
+
+    /// For every row the `m < bound` with `p[i] == m * G` (with a coset4 table: `p[i] - m * G` in E[4]), or `None` -- also for a
+    /// row that is no point of the curve.  Nothing is constant-time.
+    pub fn ed_dlog(&self, id: u64, p: &[EdwardsPoint], bound: u64) -> Result<Vec<Option<u64>>> {
+        let fp = flat_ed(p);
+        let n = p.len();
+        let (mut m, mut found) = (vec![0u64; n], vec![0u8; n]);
+        if n > 0 {
+            check(unsafe { zc_ed_dlog(self.ctx, id, fp.as_ptr(), bound, m.as_mut_ptr(), found.as_mut_ptr(), std::ptr::null_mut(), n) })?;
+        }
+        Ok(masked(m, &found))
+    }
+
+    /// The same from Ristretto encodings (the table must have been created with `coset4`): `None` where a row does not decode.
+    pub fn ris_dlog(&self, id: u64, c: &[CompressedRistretto], bound: u64) -> Result<Vec<Option<u64>>> {
+        let flat: Vec<u8> = c.iter().flat_map(|e| e.0.iter().copied()).collect();
+        let n = c.len();
+        let (mut m, mut found) = (vec![0u64; n], vec![0u8; n]);
+        if n > 0 {
+            check(unsafe { zc_ris_dlog(self.ctx, id, flat.as_ptr(), bound, m.as_mut_ptr(), found.as_mut_ptr(), std::ptr::null_mut(), n) })?;
+        }
+        Ok(masked(m, &found))
     }
 }

@@ -64,11 +64,12 @@ __attribute__((format(printf, 2, 3))) int failf(int code, const char* fmt, ...)
     return fail(code, msg);
 }
 
-#define HIP_TRY(expr)                                              \
+#define HIP_TRY_AS(expr, what)                                     \
     do {                                                           \
         hipError_t e_ = (expr);                                    \
-        if (e_ != hipSuccess) return fail(ZC_ERR_HIP, #expr, e_);  \
+        if (e_ != hipSuccess) return fail(ZC_ERR_HIP, what, e_);   \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(expr, #expr)
 
 constexpr int MAX_ARGS = 6;
 
@@ -212,6 +213,7 @@ using PinnedMem = Handle<void*, hipHostFree>;
 
 // One device slot of a context.  Created in place (zc_ctx_create) and never moved afterwards: pointers to it are taken everywhere.
 struct DevState {
+    size_t slot = 0;                    // its index among the context's slots: where a table of the context keeps this slot's copy
     int device = 0;
     Tuning tune;                        // the context's knobs (a copy per device slot)
     int cus = 256;                      // compute units (multiProcessorCount)
@@ -251,9 +253,10 @@ struct DevState {
         (void)hipStreamSynchronize(s());
         if (grp) (void)hipStreamSynchronize(grp);
     }
-    // The streams and events of a slot on HIP device `id`, which becomes the current device.
-    hipError_t open(int id, const Tuning& knobs)
+    // The streams and events of slot `index` on HIP device `id`, which becomes the current device.
+    hipError_t open(size_t index, int id, const Tuning& knobs)
     {
+        slot = index;
         device = id;
         tune = knobs;
         const auto event = [](Event& ev) { return hipEventCreateWithFlags(ev.put(), hipEventDisableTiming); };
@@ -290,34 +293,52 @@ struct RcclApi {
     const char* (*GetErrorString)(ncclResult_t) = nullptr;
 };
 
-// A fixed-base MSM table (zc_msm_bases_create): W windows of n affine records, its own allocation on device slot `slot`.
+// ---- tables the context owns and the caller names by id.  Every kind keeps its device memory the same way: `mem`, one DevBuf
+// per device slot of the context, empty where the table has no copy.
+// A fixed-base MSM table (zc_msm_bases_create): W windows of n affine records on device slot `slot` alone.
 struct MsmBases {
-    int slot = 0;
-    DevBuf recs;
+    size_t slot = 0;
     size_t n = 0;
     int c = 0, W = 0;
+    std::vector<DevBuf> mem;
 };
-std::atomic<uint64_t> g_next_bases_id{1};   // table ids: nonzero, process-wide, never reused
-// A generator set (zc_gens_create): `count` comb tables one behind the other, a copy on every device slot of the context.
+// A generator set (zc_gens_create): `count` comb tables one behind the other, a copy on every device slot.
 struct GenSet {
     size_t count = 0;
-    std::vector<DevBuf> tables;             // by device slot
+    std::vector<DevBuf> mem;
 };
 // A baby-step table (zc_dlog_create): per device slot the 2^t records and, behind them, the 2^(t+1) hash slots; the setup block
 // (stride point and launch offsets, zc_dlog_plan.h) stays on the host and travels in kernel arguments.
 struct DlogTable {
     unsigned t = 0, flags = 0;
     std::vector<zc::u32> setup;
-    std::vector<DevBuf> mem;                // by device slot
+    std::vector<DevBuf> mem;
+};
+std::atomic<uint64_t> g_next_table_id{1};   // table ids: nonzero, process-wide, one sequence for all kinds, never reused
+// The live tables of one kind in one context, by id.  Every member needs the context's lock held; `find` only reads, so that the
+// worker threads of a host batch may call it while the thread that started them holds the lock.
+template <class T>
+class Tables {
+  public:
+    uint64_t add(T&& t) { return live_.emplace(g_next_table_id.fetch_add(1), std::move(t)).first->first; }     // -> its id
+    T* find(uint64_t id)                // null: no live table of this kind and context has this id
+    {
+        const auto it = live_.find(id);
+        return it == live_.end() ? nullptr : &it->second;
+    }
+    void erase(uint64_t id) { live_.erase(id); }
+
+  private:
+    std::map<uint64_t, T> live_;
 };
 
 }  // namespace
 
 struct zc_ctx {
-    std::map<uint64_t, MsmBases> bases;   // live fixed-base tables by id (ids come from one process-wide counter: never reused);
-                                          // declared before the slots, so released after every slot has drained its streams
-    std::map<uint64_t, GenSet> gens;      // live generator sets by id, from the same counter; released after the slots too
-    std::map<uint64_t, DlogTable> dlogs;  // live baby-step tables by id, from the same counter; released after the slots too
+    Tables<MsmBases> bases;               // live fixed-base tables; declared before the slots, so released after every slot has
+                                          // drained its streams
+    Tables<GenSet> gens;                  // live generator sets; released after the slots too
+    Tables<DlogTable> dlogs;              // live baby-step tables; released after the slots too
     std::vector<DevState> devs;           // reserved at creation: the slots never move
     std::mutex mu;
     ncclComm_t comm = nullptr;          // zc_comm_init: one rank per process, device 0 of the context
@@ -1267,6 +1288,141 @@ int hash_rows_call(zc_ctx* ctx, void (*k)(const zc::HashMsg, T*, size_t), const 
     }, false);
 }
 
+// enqueue(what) -> status runs its steps on D's stream until the first failure; the stream is drained in either case, so that the
+// staging blocks declared before this call outlive whatever was enqueued.  The first error wins: the status of `enqueue`, else
+// the synchronisation's under `what`.
+template <class F>
+int enqueue_and_drain(DevState& D, const char* what, F&& enqueue)
+{
+    const int rc = enqueue(what);
+    const hipError_t synced = hipStreamSynchronize(D.s());
+    if (rc) return rc;
+    return synced == hipSuccess ? ZC_OK : fail(ZC_ERR_HIP, what, synced);
+}
+// The one small input of a create call in host memory: copied, or -- device-resident -- brought down once on its owner's stream.
+// `who` prefixes the messages about where the input lives.
+int fetch_once(zc_ctx* ctx, const char* who, const void* src, void* host, size_t bytes)
+{
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {src}, who, &owner)) return rc;
+    if (!owner) return memcpy(host, src, bytes), ZC_OK;
+    HIP_TRY(hipSetDevice(owner->device));
+    HIP_TRY(hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, owner->s()));
+    HIP_TRY(hipStreamSynchronize(owner->s()));
+    return ZC_OK;
+}
+
+// ---- the tables of a context by id: the member of the context that holds a kind, and what the calls of two kinds say about an
+// id that is no live table of theirs
+template <class T>
+using TablesOf = Tables<T> zc_ctx::*;
+constexpr const char* NO_GENS = "unknown generator set";
+constexpr const char* NO_DLOG = "unknown dlog table";
+// The table `id` names, with the context's lock held.  A row call's launch looks its table up with it a second time, under the lock
+// the batched call holds (a table destroyed since the first look is refused), and takes mem[D.slot]: that happens on run_batched's
+// worker threads too, while the calling thread holds the lock, so this only reads.
+template <class T>
+int table_find(zc_ctx* ctx, TablesOf<T> kind, uint64_t id, const char* unknown, T** t)
+{
+    *t = (ctx->*kind).find(id);
+    return *t ? ZC_OK : fail(ZC_ERR_BAD_ARG, unknown);
+}
+// A row call's first look at its table, before its argument checks: facts(table) copies out what they need under a short lock.
+template <class T, class F>
+int table_facts(zc_ctx* ctx, TablesOf<T> kind, uint64_t id, const char* unknown, F&& facts)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    T* t = nullptr;
+    if (int rc = table_find(ctx, kind, id, unknown, &t)) return rc;
+    facts(*t);
+    return ZC_OK;
+}
+// zc_msm_bases_destroy, zc_gens_destroy, zc_dlog_destroy: the stream of every slot on which the table holds memory is drained
+// before any of that memory goes; slot 0's device is current afterwards, and a failing hipFree is reported (the table is gone then).
+template <class T>
+int table_destroy(zc_ctx* ctx, TablesOf<T> kind, uint64_t id, const char* unknown)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    T* t = nullptr;
+    if (int rc = table_find(ctx, kind, id, unknown, &t)) return rc;
+    for (DevState& D : ctx->devs) {                         // work that reads the table ends before it goes
+        if (!t->mem[D.slot]) continue;
+        HIP_TRY(hipSetDevice(D.device));
+        HIP_TRY(hipStreamSynchronize(D.s()));
+    }
+    (void)hipSetDevice(ctx->devs[0].device);
+    hipError_t freed = hipSuccess;
+    for (DevBuf& b : t->mem)
+        if (const hipError_t e = b.reset(); freed == hipSuccess) freed = e;
+    (ctx->*kind).erase(id);
+    HIP_TRY(freed);
+    return ZC_OK;
+}
+
+// zc_ed_mul_gens and zc_ris_mul_gens_compress behind their pointer checks: the context, the id and n * count < 2^31 in the
+// header's order, then one lane per row of `out_per` elements.
+template <class OUT, class K>
+int mul_gens(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, OUT* out, size_t out_per, size_t n, const char* who, K kernel)
+{
+    size_t count = 0;
+    if (int rc = table_facts(ctx, &zc_ctx::gens, id, NO_GENS, [&](const GenSet& g) { count = g.count; })) return rc;
+    if (n >= ((size_t)1 << 31) / count + (((size_t)1 << 31) % count != 0)) return failf(ZC_ERR_BAD_ARG, "%s: n * count must stay below 2^31", who);
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, OUT* dout) -> int {
+        GenSet* g = nullptr;
+        if (int rc = table_find(ctx, &zc_ctx::gens, id, NO_GENS, &g)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, g->mem[D.slot].as<const zc::u32>(), (zc::u32)count, cnt);
+        return ZC_OK;
+    }, ROWS(scalars, 5 * count), ROWS(out, out_per));
+}
+// The launches of `cnt` rows of a point sum on slot D: one kernel, or -- more slices than a workgroup has lanes -- the first kernel into the
+// slot's `sum` workspace and the one that finishes the rows, both on the slot's stream (a later call's kernels come behind them;
+// a workspace that has to grow is freed first, which waits for the device).
+template <class K1, class KP, class K2, class IN, class... OUT>
+int sum_rows_launch(DevState& D, size_t cnt, size_t terms, K1 whole, KP part, K2 finish, const IN* in, OUT*... out)
+{
+    const zc::SumPlan p = zc::sum_plan(cnt, terms);
+    if (p.grid1 >= ((size_t)1 << 31)) return fail(ZC_ERR_BAD_ARG, "more rows than one launch holds");       // rows without terms only: n * terms < 2^31 bounds every other grid
+    if (p.form == zc::SUM_FORM_GROUP) {
+        hipLaunchKernelGGL(whole, dim3((unsigned)p.grid1), dim3(zc::SUM_BLOCK), 0, D.s(), in, (zc::u32)terms, (zc::u32)p.parts, out..., cnt);
+        return ZC_OK;
+    }
+    if (int rc = D.sum.grow(p.workspace_bytes)) return rc;
+    zc::u32* const ws = D.sum.as<zc::u32>();
+    hipLaunchKernelGGL(part, dim3((unsigned)p.grid1), dim3(zc::SUM_BLOCK), 0, D.s(), in, (zc::u32)terms, (zc::u32)p.parts, ws);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(finish, dim3((unsigned)p.grid2), dim3(zc::SUM_BLOCK), 0, D.s(), (const zc::u32*)ws, (zc::u32)p.blocks_per_row, out..., cnt);
+    return ZC_OK;
+}
+// The launches of `cnt` rows of a bounded discrete log on slot D, all on its stream: the slices of zc_dlog_plan.h, launch k from
+// the offset W_k.
+template <class K, class IN>
+int dlog_launches_on(zc_ctx* ctx, uint64_t id, DevState& D, K kernel, const IN* in, uint64_t bound, u64* m_out, uint8_t* found, uint8_t* ok, size_t cnt)
+{
+    DlogTable* table = nullptr;
+    if (int rc = table_find(ctx, &zc_ctx::dlogs, id, NO_DLOG, &table)) return rc;
+    const DlogTable& tb = *table;
+    const u64* const records = tb.mem[D.slot].as<const u64>();
+    zc::dlog_launch A;
+    A.table = zc::dlog_table{records, records + 4 * zc::dlog_records(tb.t), (zc::u32)tb.t};
+    A.coset4 = (tb.flags & ZC_DLOG_COSET4) ? 1u : 0u;
+    A.bound = bound;
+    static_assert(sizeof(zc::dlog_step) == 27 * sizeof(zc::u32), "a cached affine point is 27 consecutive words of the setup block");
+    memcpy(&A.S, tb.setup.data() + zc::DLOG_SETUP_STRIDE * zc::DLOG_SETUP_S, sizeof A.S);
+    const unsigned grid = (unsigned)((cnt + zc::DLOG_BLOCK - 1) / zc::DLOG_BLOCK);
+    for (uint64_t k = 0; k < zc::dlog_launches(bound, tb.t); k++) {
+        const zc::DlogSlice s = zc::dlog_slice(bound, tb.t, k);
+        A.launch = (zc::u32)k;
+        A.first = s.first;
+        A.chunks = s.chunks;
+        memcpy(&A.W, tb.setup.data() + zc::dlog_offset_word(k), sizeof A.W);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(zc::DLOG_BLOCK), 0, D.s(), in, m_out, found, ok, A, cnt);
+        HIP_TRY(hipGetLastError());
+    }
+    return ZC_OK;
+}
+
 }  // namespace
 
 // =============================================================================== C ABI
@@ -1312,7 +1468,7 @@ int zc_ctx_create(const int* devices, int ndev, zc_ctx** out)
     ctx->devs.reserve(ids.size());                           // the slots never move: pointers to them are taken everywhere
     for (int id : ids) {
         ctx->devs.emplace_back();
-        const hipError_t e = ctx->devs.back().open(id, tune);
+        const hipError_t e = ctx->devs.back().open(ctx->devs.size() - 1, id, tune);
         if (e != hipSuccess) return fail(ZC_ERR_HIP, "stream creation", e);
     }
     (void)hipSetDevice(ids[0]);
@@ -1327,7 +1483,7 @@ int zc_ctx_device(zc_ctx* ctx, int slot)
 }
 int zc_ctx_device_count(zc_ctx* ctx) { return ctx ? (int)ctx->devs.size() : fail(ZC_ERR_BAD_ARG, "null context"); }
 
-// Every slot drains its streams and releases what it holds (~DevState), then the fixed-base tables go.
+// Every slot drains its streams and releases what it holds (~DevState), then the tables of all kinds go.
 int zc_ctx_destroy(zc_ctx* ctx)
 {
     if (!ctx) return ZC_OK;
@@ -1831,15 +1987,15 @@ static int gens_build_on(DevState& D, const u64* host_points, size_t count, DevB
     u64* const dpts = stage.as<u64>();
     zc::u32* const dbad = reinterpret_cast<zc::u32*>(dpts + 20 * count);
     zc::u32 bad[ZC_GENS_MAX] = {};
-    hipError_t e = hipMemcpyAsync(dpts, host_points, count * 160, hipMemcpyHostToDevice, D.s());
-    if (e == hipSuccess) e = hipMemsetAsync(dbad, 0, count * sizeof(zc::u32), D.s());
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(zc::k_gens_table_build, dim3((unsigned)count), dim3(zc::ZC_BASE_ENTRIES), 0, D.s(), (const u64*)dpts, tables.as<zc::u32>(), dbad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(bad, dbad, count * sizeof(zc::u32), hipMemcpyDeviceToHost, D.s());
-    const hipError_t synced = hipStreamSynchronize(D.s());
-    if (e != hipSuccess || synced != hipSuccess) return fail(ZC_ERR_HIP, "zc_gens_create: table build", e != hipSuccess ? e : synced);
+    if (int rc = enqueue_and_drain(D, "zc_gens_create: table build", [&](const char* what) -> int {
+            HIP_TRY_AS(hipMemcpyAsync(dpts, host_points, count * 160, hipMemcpyHostToDevice, D.s()), what);
+            HIP_TRY_AS(hipMemsetAsync(dbad, 0, count * sizeof(zc::u32), D.s()), what);
+            hipLaunchKernelGGL(zc::k_gens_table_build, dim3((unsigned)count), dim3(zc::ZC_BASE_ENTRIES), 0, D.s(), (const u64*)dpts, tables.as<zc::u32>(), dbad);
+            HIP_TRY_AS(hipGetLastError(), what);
+            HIP_TRY_AS(hipMemcpyAsync(bad, dbad, count * sizeof(zc::u32), hipMemcpyDeviceToHost, D.s()), what);
+            return ZC_OK;
+        }))
+        return rc;
     for (size_t j = count; j-- > 0;)
         if (bad[j]) *first_bad = (int)j;
     return ZC_OK;
@@ -1851,121 +2007,40 @@ int zc_gens_create(zc_ctx* ctx, const uint64_t* points, size_t count, uint64_t* 
     if (count < 1 || count > ZC_GENS_MAX) return fail(ZC_ERR_BAD_ARG, "zc_gens_create: count must be 1 .. ZC_GENS_MAX");
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    DevState* owner = nullptr;
-    if (int rc = owner_of(ctx, {points}, "zc_gens_create: ", &owner)) return rc;
     u64 host[20 * ZC_GENS_MAX];                             // device-resident points come down once and go up to every slot
-    if (owner) {
-        HIP_TRY(hipSetDevice(owner->device));
-        HIP_TRY(hipMemcpyAsync(host, points, count * 160, hipMemcpyDeviceToHost, owner->s()));
-        HIP_TRY(hipStreamSynchronize(owner->s()));
-    } else {
-        memcpy(host, points, count * 160);
-    }
-    GenSet g;
-    g.count = count;
-    g.tables.resize(ctx->devs.size());
+    if (int rc = fetch_once(ctx, "zc_gens_create: ", points, host, count * 160)) return rc;
+    GenSet g{count, std::vector<DevBuf>(ctx->devs.size())};
     int first_bad = -1;
     int rc = ZC_OK;
-    for (size_t di = 0; di < ctx->devs.size() && !rc && first_bad < 0; di++) rc = gens_build_on(ctx->devs[di], host, count, g.tables[di], &first_bad);
+    for (size_t di = 0; di < ctx->devs.size() && !rc && first_bad < 0; di++) rc = gens_build_on(ctx->devs[di], host, count, g.mem[di], &first_bad);
     (void)hipSetDevice(ctx->devs[0].device);
     if (rc) return rc;
     if (first_bad >= 0) return failf(ZC_ERR_BAD_ARG, "zc_gens_create: generator %d is not a point of the curve", first_bad);
-    const uint64_t id = g_next_bases_id.fetch_add(1);
-    ctx->gens.emplace(id, std::move(g));
-    *id_out = id;
+    *id_out = ctx->gens.add(std::move(g));
     return ZC_OK;
 }
-int zc_gens_destroy(zc_ctx* ctx, uint64_t id)
-{
-    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    auto it = ctx->gens.find(id);
-    if (it == ctx->gens.end()) return fail(ZC_ERR_BAD_ARG, "unknown generator set");
-    for (DevState& D : ctx->devs) {                         // work that reads the tables ends before they go
-        HIP_TRY(hipSetDevice(D.device));
-        HIP_TRY(hipStreamSynchronize(D.s()));
-    }
-    (void)hipSetDevice(ctx->devs[0].device);
-    ctx->gens.erase(it);
-    return ZC_OK;
-}
-// The checks of the two row calls behind their pointers, in the header's order, and the set's term count.
-static int gens_row_args(zc_ctx* ctx, uint64_t id, size_t n, const char* who, size_t* count)
-{
-    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        auto it = ctx->gens.find(id);
-        if (it == ctx->gens.end()) return fail(ZC_ERR_BAD_ARG, "unknown generator set");
-        *count = it->second.count;
-    }
-    if (n >= ((size_t)1 << 31) / *count + (((size_t)1 << 31) % *count != 0)) return failf(ZC_ERR_BAD_ARG, "%s: n * count must stay below 2^31", who);
-    return ZC_OK;
-}
-// The set's tables on slot D, looked up again under the lock the batched call holds (a set destroyed in between is refused).
-static int gens_tables(zc_ctx* ctx, uint64_t id, DevState& D, const zc::u32** tables)
-{
-    auto it = ctx->gens.find(id);
-    if (it == ctx->gens.end()) return fail(ZC_ERR_BAD_ARG, "unknown generator set");
-    *tables = it->second.tables[(size_t)(&D - ctx->devs.data())].as<const zc::u32>();
-    return ZC_OK;
-}
+int zc_gens_destroy(zc_ctx* ctx, uint64_t id) { return table_destroy(ctx, &zc_ctx::gens, id, NO_GENS); }
 int zc_ed_mul_gens(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, uint64_t* out, size_t n)
 {
     REQUIRE(scalars);
     REQUIRE(out);
-    size_t count = 0;
-    if (int rc = gens_row_args(ctx, id, n, "zc_ed_mul_gens", &count)) return rc;
-    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, u64* dout) -> int {
-        const zc::u32* t = nullptr;
-        if (int rc = gens_tables(ctx, id, D, &t)) return rc;
-        hipLaunchKernelGGL(zc::k_ed_mul_gens, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, (zc::u32)count, cnt);
-        return ZC_OK;
-    }, ROWS(scalars, 5 * count), ROWS(out, 20));
+    return mul_gens(ctx, id, scalars, out, 20, n, "zc_ed_mul_gens", zc::k_ed_mul_gens);
 }
 int zc_ris_mul_gens_compress(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, uint8_t* out32, size_t n)
 {
     REQUIRE(scalars);
     REQUIRE(out32);
-    size_t count = 0;
-    if (int rc = gens_row_args(ctx, id, n, "zc_ris_mul_gens_compress", &count)) return rc;
-    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dk, uint8_t* dout) -> int {
-        const zc::u32* t = nullptr;
-        if (int rc = gens_tables(ctx, id, D, &t)) return rc;
-        hipLaunchKernelGGL(zc::k_ris_mul_gens_compress, dim3(grid_for(cnt)), dim3(zc::ZC_BLOCK), 0, D.s(), dk, dout, t, (zc::u32)count, cnt);
-        return ZC_OK;
-    }, ROWS(scalars, 5 * count), ROWS(out32, 32));
+    return mul_gens(ctx, id, scalars, out32, 32, n, "zc_ris_mul_gens_compress", zc::k_ris_mul_gens_compress);
 }
 
 // ---- point sums (zerocaf_hip_ext_sum_rows.h): out[i] = P_i0 + P_i1 + ... in the order zc_sum_plan.h fixes for `terms` (kernels:
-// zc_sum.hip.h).  The checks behind the pointers, in the header's order.
+// zc_sum.hip.h; launches: sum_rows_launch).  The checks behind the pointers, in the header's order.
 static int sum_rows_args(zc_ctx* ctx, size_t n, size_t terms, const char* who)
 {
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     if (zc::sum_too_large(n, terms)) return failf(ZC_ERR_BAD_ARG, "%s: n * terms must stay below 2^31", who);
     return ZC_OK;
 }
-// The launches of `cnt` rows on slot D: one kernel, or -- more slices than a workgroup has lanes -- the first kernel into the
-// slot's `sum` workspace and the one that finishes the rows, both on the slot's stream (a later call's kernels come behind them;
-// a workspace that has to grow is freed first, which waits for the device).
-}  // extern "C"
-template <class K1, class KP, class K2, class IN, class... OUT>
-static int sum_rows_launch(DevState& D, size_t cnt, size_t terms, K1 whole, KP part, K2 finish, const IN* in, OUT*... out)
-{
-    const zc::SumPlan p = zc::sum_plan(cnt, terms);
-    if (p.grid1 >= ((size_t)1 << 31)) return fail(ZC_ERR_BAD_ARG, "more rows than one launch holds");       // rows without terms only: n * terms < 2^31 bounds every other grid
-    if (p.form == zc::SUM_FORM_GROUP) {
-        hipLaunchKernelGGL(whole, dim3((unsigned)p.grid1), dim3(zc::SUM_BLOCK), 0, D.s(), in, (zc::u32)terms, (zc::u32)p.parts, out..., cnt);
-        return ZC_OK;
-    }
-    if (int rc = D.sum.grow(p.workspace_bytes)) return rc;
-    zc::u32* const ws = D.sum.as<zc::u32>();
-    hipLaunchKernelGGL(part, dim3((unsigned)p.grid1), dim3(zc::SUM_BLOCK), 0, D.s(), in, (zc::u32)terms, (zc::u32)p.parts, ws);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(finish, dim3((unsigned)p.grid2), dim3(zc::SUM_BLOCK), 0, D.s(), (const zc::u32*)ws, (zc::u32)p.blocks_per_row, out..., cnt);
-    return ZC_OK;
-}
-extern "C" {
 int zc_ed_sum_rows(zc_ctx* ctx, const uint64_t* points, size_t terms, uint64_t* out, size_t n)
 {
     REQUIRE(points);
@@ -2005,27 +2080,27 @@ static int dlog_compute_on(DevState& D, const u64* host_point, DlogTable& tb, st
     u64* const dpoint = stage.as<u64>();
     zc::u32* const dsetup = reinterpret_cast<zc::u32*>(dpoint + 20);
     tb.setup.assign(zc::DLOG_SETUP_WORDS, 0);
-    hipError_t e = hipMemcpyAsync(dpoint, host_point, 160, hipMemcpyHostToDevice, D.s());
-    if (e == hipSuccess) e = hipMemsetAsync(dsetup, 0, zc::DLOG_SETUP_WORDS * sizeof(zc::u32), D.s());
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(zc::k_dlog_setup, dim3(1), dim3(zc::DLOG_BLOCK), 0, D.s(), (const u64*)dpoint, dsetup, (zc::u32)tb.t, (zc::u32)tb.flags);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(tb.setup.data(), dsetup, zc::DLOG_SETUP_WORDS * sizeof(zc::u32), hipMemcpyDeviceToHost, D.s());
-    hipError_t synced = hipStreamSynchronize(D.s());
-    if (e != hipSuccess || synced != hipSuccess) return fail(ZC_ERR_HIP, "zc_dlog_create: setup", e != hipSuccess ? e : synced);
+    if (int rc = enqueue_and_drain(D, "zc_dlog_create: setup", [&](const char* what) -> int {
+            HIP_TRY_AS(hipMemcpyAsync(dpoint, host_point, 160, hipMemcpyHostToDevice, D.s()), what);
+            HIP_TRY_AS(hipMemsetAsync(dsetup, 0, zc::DLOG_SETUP_WORDS * sizeof(zc::u32), D.s()), what);
+            hipLaunchKernelGGL(zc::k_dlog_setup, dim3(1), dim3(zc::DLOG_BLOCK), 0, D.s(), (const u64*)dpoint, dsetup, (zc::u32)tb.t, (zc::u32)tb.flags);
+            HIP_TRY_AS(hipGetLastError(), what);
+            HIP_TRY_AS(hipMemcpyAsync(tb.setup.data(), dsetup, zc::DLOG_SETUP_WORDS * sizeof(zc::u32), hipMemcpyDeviceToHost, D.s()), what);
+            return ZC_OK;
+        }))
+        return rc;
     if (tb.setup[0] == zc::DLOG_SETUP_NOT_A_POINT) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: not a point of the curve");
     if (tb.setup[0] != zc::DLOG_SETUP_OK) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: generator lies in E[8]");
     if (int rc = tb.mem[0].alloc(zc::dlog_table_bytes(tb.t), "zc_dlog_create: hipMalloc(table)")) return rc;
     records.resize(4 * zc::dlog_records(tb.t));
     const size_t lanes = zc::dlog_build_lanes(tb.t);
-    hipLaunchKernelGGL(zc::k_dlog_records, dim3((unsigned)((lanes + zc::DLOG_BLOCK - 1) / zc::DLOG_BLOCK)), dim3(zc::DLOG_BLOCK), 0, D.s(), (const zc::u32*)dsetup,
-                       tb.mem[0].as<u64>(), (zc::u32)tb.t);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(records.data(), tb.mem[0].as<u64>(), zc::dlog_record_bytes(tb.t), hipMemcpyDeviceToHost, D.s());
-    synced = hipStreamSynchronize(D.s());
-    if (e != hipSuccess || synced != hipSuccess) return fail(ZC_ERR_HIP, "zc_dlog_create: records", e != hipSuccess ? e : synced);
-    return ZC_OK;
+    return enqueue_and_drain(D, "zc_dlog_create: records", [&](const char* what) -> int {
+        hipLaunchKernelGGL(zc::k_dlog_records, dim3((unsigned)((lanes + zc::DLOG_BLOCK - 1) / zc::DLOG_BLOCK)), dim3(zc::DLOG_BLOCK), 0, D.s(), (const zc::u32*)dsetup,
+                           tb.mem[0].as<u64>(), (zc::u32)tb.t);
+        HIP_TRY_AS(hipGetLastError(), what);
+        HIP_TRY_AS(hipMemcpyAsync(records.data(), tb.mem[0].as<u64>(), zc::dlog_record_bytes(tb.t), hipMemcpyDeviceToHost, D.s()), what);
+        return ZC_OK;
+    });
 }
 int zc_dlog_create(zc_ctx* ctx, const uint64_t* point, unsigned table_bits, unsigned flags, uint64_t* id_out)
 {
@@ -2035,20 +2110,9 @@ int zc_dlog_create(zc_ctx* ctx, const uint64_t* point, unsigned table_bits, unsi
     if (flags & ~ZC_DLOG_COSET4) return fail(ZC_ERR_BAD_ARG, "zc_dlog_create: unknown flag bits");
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    DevState* owner = nullptr;
-    if (int rc = owner_of(ctx, {point}, "zc_dlog_create: ", &owner)) return rc;
     u64 host[20];                                           // a device-resident point comes down once
-    if (owner) {
-        HIP_TRY(hipSetDevice(owner->device));
-        HIP_TRY(hipMemcpyAsync(host, point, 160, hipMemcpyDeviceToHost, owner->s()));
-        HIP_TRY(hipStreamSynchronize(owner->s()));
-    } else {
-        memcpy(host, point, 160);
-    }
-    DlogTable tb;
-    tb.t = table_bits;
-    tb.flags = flags;
-    tb.mem.resize(ctx->devs.size());
+    if (int rc = fetch_once(ctx, "zc_dlog_create: ", point, host, 160)) return rc;
+    DlogTable tb{table_bits, flags, {}, std::vector<DevBuf>(ctx->devs.size())};
     std::vector<u64> records, slots;
     int rc = dlog_compute_on(ctx->devs[0], host, tb, records);
     if (!rc) {
@@ -2058,85 +2122,34 @@ int zc_dlog_create(zc_ctx* ctx, const uint64_t* point, unsigned table_bits, unsi
     // the slots behind the records on every device slot; the records too where they were not computed
     for (size_t di = 0; di < ctx->devs.size() && !rc; di++) {
         DevState& D = ctx->devs[di];
-        if (di) rc = ring_check(D);
-        if (rc) break;
-        hipError_t e = hipSetDevice(D.device);
-        if (e == hipSuccess && di) {
-            rc = tb.mem[di].alloc(zc::dlog_table_bytes(tb.t), "zc_dlog_create: hipMalloc(table)");
-            if (rc) break;
-            e = hipMemcpyAsync(tb.mem[di].as<u64>(), records.data(), zc::dlog_record_bytes(tb.t), hipMemcpyHostToDevice, D.s());
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(tb.mem[di].as<u64>() + 4 * zc::dlog_records(tb.t), slots.data(), zc::dlog_slot_bytes(tb.t), hipMemcpyHostToDevice, D.s());
-        const hipError_t synced = hipStreamSynchronize(D.s());
-        if (e != hipSuccess || synced != hipSuccess) rc = fail(ZC_ERR_HIP, "zc_dlog_create: table upload", e != hipSuccess ? e : synced);
+        DevBuf& mem = tb.mem[di];
+        if (di && (rc = ring_check(D))) break;              // slot 0: dlog_compute_on has asked
+        rc = enqueue_and_drain(D, "zc_dlog_create: table upload", [&](const char* what) -> int {
+            HIP_TRY_AS(hipSetDevice(D.device), what);
+            if (di) {
+                if (int arc = mem.alloc(zc::dlog_table_bytes(tb.t), "zc_dlog_create: hipMalloc(table)")) return arc;
+                HIP_TRY_AS(hipMemcpyAsync(mem.as<u64>(), records.data(), zc::dlog_record_bytes(tb.t), hipMemcpyHostToDevice, D.s()), what);
+            }
+            HIP_TRY_AS(hipMemcpyAsync(mem.as<u64>() + 4 * zc::dlog_records(tb.t), slots.data(), zc::dlog_slot_bytes(tb.t), hipMemcpyHostToDevice, D.s()), what);
+            return ZC_OK;
+        });
     }
     (void)hipSetDevice(ctx->devs[0].device);
     if (rc) return rc;
-    const uint64_t id = g_next_bases_id.fetch_add(1);
-    ctx->dlogs.emplace(id, std::move(tb));
-    *id_out = id;
+    *id_out = ctx->dlogs.add(std::move(tb));
     return ZC_OK;
 }
-int zc_dlog_destroy(zc_ctx* ctx, uint64_t id)
-{
-    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    auto it = ctx->dlogs.find(id);
-    if (it == ctx->dlogs.end()) return fail(ZC_ERR_BAD_ARG, "unknown dlog table");
-    for (DevState& D : ctx->devs) {                         // work that reads the table ends before it goes
-        HIP_TRY(hipSetDevice(D.device));
-        HIP_TRY(hipStreamSynchronize(D.s()));
-    }
-    (void)hipSetDevice(ctx->devs[0].device);
-    ctx->dlogs.erase(it);
-    return ZC_OK;
-}
+int zc_dlog_destroy(zc_ctx* ctx, uint64_t id) { return table_destroy(ctx, &zc_ctx::dlogs, id, NO_DLOG); }
 // The checks of the two row calls behind their pointers, in the header's order.
 static int dlog_row_args(zc_ctx* ctx, uint64_t id, uint64_t bound, size_t n, bool wire, const char* who)
 {
-    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     unsigned t = 0, flags = 0;
-    {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        auto it = ctx->dlogs.find(id);
-        if (it == ctx->dlogs.end()) return fail(ZC_ERR_BAD_ARG, "unknown dlog table");
-        t = it->second.t;
-        flags = it->second.flags;
-    }
+    if (int rc = table_facts(ctx, &zc_ctx::dlogs, id, NO_DLOG, [&](const DlogTable& tb) { t = tb.t, flags = tb.flags; })) return rc;
     if (wire && !(flags & ZC_DLOG_COSET4)) return fail(ZC_ERR_BAD_ARG, "zc_ris_dlog needs a ZC_DLOG_COSET4 table");
     if (!zc::dlog_bound_ok(bound, t)) return failf(ZC_ERR_BAD_ARG, "%s: bound must be 1 .. 2^table_bits * ZC_DLOG_MAX_STEPS", who);
     if (n >= ((size_t)1 << 31)) return failf(ZC_ERR_BAD_ARG, "%s: n must stay below 2^31", who);
     return ZC_OK;
 }
-// The launches of `cnt` rows on slot D, all on its stream: the slices of zc_dlog_plan.h, launch k from the offset W_k.  The table
-// is looked up again under the lock the batched call holds (a table destroyed in between is refused).
-}  // extern "C"
-template <class K, class IN>
-static int dlog_launches_on(zc_ctx* ctx, uint64_t id, DevState& D, K kernel, const IN* in, uint64_t bound, u64* m_out, uint8_t* found, uint8_t* ok, size_t cnt)
-{
-    auto it = ctx->dlogs.find(id);
-    if (it == ctx->dlogs.end()) return fail(ZC_ERR_BAD_ARG, "unknown dlog table");
-    const DlogTable& tb = it->second;
-    const u64* const records = tb.mem[(size_t)(&D - ctx->devs.data())].as<const u64>();
-    zc::dlog_launch A;
-    A.table = zc::dlog_table{records, records + 4 * zc::dlog_records(tb.t), (zc::u32)tb.t};
-    A.coset4 = (tb.flags & ZC_DLOG_COSET4) ? 1u : 0u;
-    A.bound = bound;
-    static_assert(sizeof(zc::dlog_step) == 27 * sizeof(zc::u32), "a cached affine point is 27 consecutive words of the setup block");
-    memcpy(&A.S, tb.setup.data() + zc::DLOG_SETUP_STRIDE * zc::DLOG_SETUP_S, sizeof A.S);
-    const unsigned grid = (unsigned)((cnt + zc::DLOG_BLOCK - 1) / zc::DLOG_BLOCK);
-    for (uint64_t k = 0; k < zc::dlog_launches(bound, tb.t); k++) {
-        const zc::DlogSlice s = zc::dlog_slice(bound, tb.t, k);
-        A.launch = (zc::u32)k;
-        A.first = s.first;
-        A.chunks = s.chunks;
-        memcpy(&A.W, tb.setup.data() + zc::dlog_offset_word(k), sizeof A.W);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(zc::DLOG_BLOCK), 0, D.s(), in, m_out, found, ok, A, cnt);
-        HIP_TRY(hipGetLastError());
-    }
-    return ZC_OK;
-}
-extern "C" {
 int zc_ed_dlog(zc_ctx* ctx, uint64_t id, const uint64_t* p, uint64_t bound, uint64_t* m_out, uint8_t* found, uint8_t* ok, size_t n)
 {
     REQUIRE(p);
@@ -2371,53 +2384,34 @@ int zc_msm_bases_create(zc_ctx* ctx, const uint64_t* points, size_t n, int windo
     DevState& D = owner ? *owner : ctx->devs[0];
     if (int rc = ring_check(D)) return rc;
     HIP_TRY(hipSetDevice(D.device));
-    MsmBases t;
-    t.slot = (int)(&D - ctx->devs.data());
-    t.n = n;
-    t.c = c;
-    t.W = W;
+    MsmBases t{D.slot, n, c, W, std::vector<DevBuf>(ctx->devs.size())};
+    DevBuf& recs = t.mem[t.slot];
     // window 0 = the points (copied: 16-byte aligned, plain), window j = 2^c times window j - 1, each normalised into its part of
-    // the table; the two n-point buffers live for this call only
+    // the table; the two n-point buffers live for this call only.  Whatever was enqueued is through before the buffers go: the
+    // two point arrays with this call, the table too when a step failed
     DevBuf pts[2];
-    auto enqueue = [&]() -> int {
-        if (int rc = t.recs.alloc(n * (size_t)W * ZC_MSM_REC_STRIDE, "zc_msm_bases_create: hipMalloc(table)")) return rc;
-        for (DevBuf& b : pts)
-            if (int rc = b.alloc(n * 160, "zc_msm_bases_create: hipMalloc(points)")) return rc;
-        hipError_t e = hipMemcpyAsync(pts[0].as<void>(), points, n * 160, owner ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, D.s());
-        if (e != hipSuccess) return fail(ZC_ERR_HIP, "zc_msm_bases_create: copy of the points", e);
-        const zc::u32 rec_words = ZC_MSM_REC_STRIDE / 4;
-        for (int j = 0; j < W; j++) {
-            if (j) hipLaunchKernelGGL(zc::k_msm_fixed_double, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), pts[(j - 1) & 1].as<const u64>(), pts[j & 1].as<u64>(), n, c);
-            msm_prepare_affine(D.s(), pts[j & 1].as<const u64>(), t.recs.as<zc::u32>() + (size_t)j * n * rec_words, n, D.tune, rec_words);
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(ZC_ERR_HIP, "zc_msm_bases_create: table build", e);
-        return ZC_OK;
-    };
-    // whatever was enqueued is through before the buffers go: the two point arrays with this call, the table too when a step failed
-    int rc = enqueue();
-    const hipError_t e = hipStreamSynchronize(D.s());
-    if (!rc && e != hipSuccess) rc = fail(ZC_ERR_HIP, "zc_msm_bases_create: table build", e);
-    if (rc) return rc;
-    const uint64_t id = g_next_bases_id.fetch_add(1);
-    ctx->bases.emplace(id, std::move(t));
-    *id_out = id;
+    if (int rc = enqueue_and_drain(D, "zc_msm_bases_create: table build", [&](const char* what) -> int {
+            if (int arc = recs.alloc(n * (size_t)W * ZC_MSM_REC_STRIDE, "zc_msm_bases_create: hipMalloc(table)")) return arc;
+            for (DevBuf& b : pts)
+                if (int arc = b.alloc(n * 160, "zc_msm_bases_create: hipMalloc(points)")) return arc;
+            const hipError_t e = hipMemcpyAsync(pts[0].as<void>(), points, n * 160, owner ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, D.s());
+            if (e != hipSuccess) return fail(ZC_ERR_HIP, "zc_msm_bases_create: copy of the points", e);
+            const zc::u32 rec_words = ZC_MSM_REC_STRIDE / 4;
+            for (int j = 0; j < W; j++) {
+                if (j) hipLaunchKernelGGL(zc::k_msm_fixed_double, dim3(grid_for(n)), dim3(zc::ZC_BLOCK), 0, D.s(), pts[(j - 1) & 1].as<const u64>(), pts[j & 1].as<u64>(), n, c);
+                msm_prepare_affine(D.s(), pts[j & 1].as<const u64>(), recs.as<zc::u32>() + (size_t)j * n * rec_words, n, D.tune, rec_words);
+            }
+            HIP_TRY_AS(hipGetLastError(), what);
+            return ZC_OK;
+        }))
+        return rc;
+    *id_out = ctx->bases.add(std::move(t));
     return ZC_OK;
 }
 
 int zc_msm_bases_destroy(zc_ctx* ctx, uint64_t id)
 {
-    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    auto it = ctx->bases.find(id);
-    if (it == ctx->bases.end()) return fail(ZC_ERR_BAD_ARG, "zc_msm_bases_destroy: no live table of this context has this id");
-    DevState& D = ctx->devs[(size_t)it->second.slot];
-    HIP_TRY(hipSetDevice(D.device));
-    HIP_TRY(hipStreamSynchronize(D.s()));
-    const hipError_t freed = it->second.recs.reset();
-    ctx->bases.erase(it);
-    HIP_TRY(freed);
-    return ZC_OK;
+    return table_destroy(ctx, &zc_ctx::bases, id, "zc_msm_bases_destroy: no live table of this context has this id");
 }
 
 // out_points[b] = sum_i k[b][i] P_i: digits of every vector (one launch), ONE key sort over the batch's vectors as its windows,
@@ -2426,17 +2420,17 @@ int zc_msm_fixed(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, size_t batch
 {
     if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    auto it = ctx->bases.find(id);
-    if (it == ctx->bases.end()) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: no live table of this context has this id");
+    MsmBases* found = nullptr;
+    if (int rc = table_find(ctx, &zc_ctx::bases, id, "zc_msm_fixed: no live table of this context has this id", &found)) return rc;
     if (batch == 0) return ZC_OK;
     REQUIRE(scalars); REQUIRE(out_points);
-    const MsmBases& t = it->second;
+    const MsmBases& t = *found;
     const size_t n = t.n;
     const int c = t.c;
     const zc::MsmLimit limit = zc::msm_index_limit(0, zc::msm_sat_mul(batch, n * (size_t)t.W), zc::msm_sat_mul(batch, (size_t)1 << (c - 1)));
     if (limit == zc::MSM_LIMIT_PAIRS) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x n x W does not fit 32-bit pair indices");
     if (limit == zc::MSM_LIMIT_KEYS) return fail(ZC_ERR_BAD_ARG, "zc_msm_fixed: batch x 2^(c-1) buckets do not fit 32-bit bucket keys");
-    DevState& D = ctx->devs[(size_t)t.slot];
+    DevState& D = ctx->devs[t.slot];
     DevState* owner = nullptr;
     if (int rc = owner_of(ctx, {scalars}, "zc_msm_fixed: ", &owner)) return rc;
     if (owner && owner->device != D.device) return fail(ZC_ERR_MIXED_MEM, "zc_msm_fixed: scalars on another device than the table");
@@ -2449,7 +2443,7 @@ int zc_msm_fixed(zc_ctx* ctx, uint64_t id, const uint64_t* scalars, size_t batch
     HIP_TRY(hipMemsetAsync(ws.present, 0, fp.nb, D.s()));
     if (int rc = msm_sort(D, D.s(), fp.sort, 0, (int)batch, ws.digits, ws.pairs_a, ws.pairs_b, ws.sort_table, fp.sort.table_words, ws.sort_sums)) return rc;
     u64* sums = nullptr;
-    if (int rc = msm_reduce_windows(D, msm_reduce_bufs(fp, ws, t.recs.as<const zc::u32>()), msm_reduce_flat(fp, ws), &sums)) return rc;
+    if (int rc = msm_reduce_windows(D, msm_reduce_bufs(fp, ws, t.mem[t.slot].as<const zc::u32>()), msm_reduce_flat(fp, ws), &sums)) return rc;
     // the folds leave the batch's sums as canonical extended points, one per vector in order
     HIP_TRY(hipMemcpyAsync(out_points, sums, batch * 160, hipMemcpyDeviceToHost, D.s()));
     HIP_TRY(hipStreamSynchronize(D.s()));

@@ -42,6 +42,7 @@ def test_library_exports_every_declared_symbol(lib):
     out = subprocess.check_output(["nm", "-D", "--defined-only", z.LIB_PATH], text=True)
     exported = set(re.findall(r"\bT (zc_[a-z0-9_]+)", out))
     assert set(syms) <= exported
+    assert "sum_rows_launch" not in out and "dlog_launches_on" not in out and "_GLOBAL__N_" not in out      # the host helpers stay internal
 
 
 def test_no_cpu_fallback_and_no_oracle_linkage(lib):

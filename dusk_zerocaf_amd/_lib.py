@@ -151,6 +151,12 @@ EXT_DLOG_SIGNATURES = {
     "zc_ed_dlog": [C.c_uint64, _u64p, C.c_uint64, _u64p, _u8p, _u8p, _n],
     "zc_ris_dlog": [C.c_uint64, _u8p, C.c_uint64, _u64p, _u8p, _u8p, _n],
 }
+# scalar vector ops (include/zerocaf_hip_scvec.h, a header of its own): the rows, terms, [flags,] out and n
+EXT_SCVEC_SIGNATURES = {
+    "zc_sc_sum_rows": [_u64p, _n, _u64p, _n],
+    "zc_sc_dot_rows": [_u64p, _u64p, _n, C.c_uint, _u64p, _n],
+    "zc_sc_powers": [_u64p, _n, _u64p, _n],
+}
 CONTEXT_SYMBOLS = ["zc_ctx_create", "zc_ctx_destroy", "zc_ctx_device", "zc_ctx_device_count", "zc_ctx_set_stream", "zc_ctx_synchronize",
                    "zc_device_count", "zc_last_error", "zc_version", "zc_host_register", "zc_host_unregister",
                    "zc_comm_unique_id"]
@@ -200,7 +206,7 @@ def _bind(path: str) -> C.CDLL:
     lib.zc_host_register.argtypes = [C.c_void_p, C.c_size_t]
     lib.zc_host_unregister.argtypes = [C.c_void_p]
     lib.zc_comm_unique_id.argtypes = [C.c_void_p]
-    for name, sig in list(SIGNATURES.items()) + list(SCALAR_EXT_SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT_SUM_SIGNATURES.items()) + list(EXT_HASH_SIGNATURES.items()) + list(EXT_SHARED_SIGNATURES.items()) + list(EXT_SHARED_LINCOMB_SIGNATURES.items()) + list(EXT_GENS_SIGNATURES.items()) + list(EXT_SUM_ROWS_SIGNATURES.items()) + list(EXT_DLOG_SIGNATURES.items()):
+    for name, sig in list(SIGNATURES.items()) + list(SCALAR_EXT_SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT_SUM_SIGNATURES.items()) + list(EXT_HASH_SIGNATURES.items()) + list(EXT_SHARED_SIGNATURES.items()) + list(EXT_SHARED_LINCOMB_SIGNATURES.items()) + list(EXT_GENS_SIGNATURES.items()) + list(EXT_SUM_ROWS_SIGNATURES.items()) + list(EXT_DLOG_SIGNATURES.items()) + list(EXT_SCVEC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = [_ctx] + sig
         fn.restype = C.c_int

@@ -11,12 +11,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzerocaf_hip.so")
 SOURCES = ["zerocaf_hip.hip"]
 DEPS = ["zerocaf_hip.hip", "zc_kernels.hip.h", "zc_msm.hip.h", "zc_msm_plan.h", "zc_launch_plan.h", "zc_sort.hip.h", "zc_quad.hip.h", "zc_curve.hip.h", "zc_arith.hip.h",
-        "zc_constants.hip.h", "zc_ris_batch.hip.h", "zc_hash.hip.h", "zc_shared.hip.h", "zc_shared_scalar.h", "zc_gens.hip.h", "zc_sum.hip.h", "zc_sum_plan.h", "zc_dlog.hip.h", "zc_dlog_plan.h",
+        "zc_constants.hip.h", "zc_ris_batch.hip.h", "zc_hash.hip.h", "zc_shared.hip.h", "zc_shared_scalar.h", "zc_gens.hip.h", "zc_sum.hip.h", "zc_sum_plan.h", "zc_dlog.hip.h", "zc_dlog_plan.h", "zc_scvec.hip.h", "zc_scvec_plan.h",
         os.path.join("..", "..", "include", "zerocaf_hip.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext.h"),
         os.path.join("..", "..", "include", "zerocaf_hip_ext_sum.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext_hash.h"),
         os.path.join("..", "..", "include", "zerocaf_hip_ext_shared.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext_shared_lincomb.h"),
         os.path.join("..", "..", "include", "zerocaf_hip_ext_gens.h"), os.path.join("..", "..", "include", "zerocaf_hip_ext_sum_rows.h"),
-        os.path.join("..", "..", "include", "zerocaf_hip_dlog.h")]
+        os.path.join("..", "..", "include", "zerocaf_hip_dlog.h"), os.path.join("..", "..", "include", "zerocaf_hip_scvec.h")]
 
 
 def hipcc() -> str:

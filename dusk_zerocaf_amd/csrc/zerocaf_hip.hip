@@ -27,6 +27,7 @@
 #include "../../include/zerocaf_hip.h"
 #include "../../include/zerocaf_hip_ext.h"
 #include "../../include/zerocaf_hip_dlog.h"
+#include "../../include/zerocaf_hip_scvec.h"
 #include "zc_kernels.hip.h"
 #include "zc_msm.hip.h"
 #include "zc_ris_batch.hip.h"
@@ -35,6 +36,7 @@
 #include "zc_gens.hip.h"
 #include "zc_sum.hip.h"
 #include "zc_dlog.hip.h"
+#include "zc_scvec.hip.h"
 
 using zc::u64;
 using zc::MsmBucketPlan, zc::MsmPlan, zc::MsmSortPlan;
@@ -227,6 +229,8 @@ struct DevState {
     DevBuf msm;                         // the MSM workspace: bucket method, or the products and folds of a small shard / batch
     DevBuf ris_sum;                     // zc_ris_lincomb_sum: the MSM inputs it prepares (records, scalars, flags, base-term partials)
     DevBuf sum;                         // zc_ed_sum_rows / zc_ris_sum_rows: the partials between their two kernels (zc_sum_plan.h)
+    DevBuf scvec;                       // zc_sc_sum_rows / zc_sc_dot_rows: the partials between their two kernels (zc_scvec_plan.h)
+    DevBuf scvec_b;                     // zc_sc_dot_rows from host arrays: the shared row of b, uploaded once per call
     DevBuf fast;                        // windowed-core tables: ring of wave slots, 256 MB (zc_kernels.hip.h)
     DevBuf ring;                        // tickets and slot flags of the table ring (+ the device address of the error word)
     PinnedMem ring_err;                 // the ring's error word: pinned host memory, written by a wave that gave up
@@ -2169,6 +2173,100 @@ int zc_ris_dlog(zc_ctx* ctx, uint64_t id, const uint8_t* in32, uint64_t bound, u
     return batched(ctx, n, true, [&](DevState& D, size_t cnt, const uint8_t* din, u64* dm, uint8_t* df, uint8_t* dok) -> int {
         return dlog_launches_on(ctx, id, D, zc::k_ris_dlog, din, bound, dm, df, dok, cnt);
     }, ROWS(in32, 32), ROWS(m_out, 1), ROWS(found, 1), OPT_ROWS(ok, 1));
+}
+
+// ---- scalar vector ops (zerocaf_hip_scvec.h): row sums, inner products and power rows mod L (kernels: zc_scvec.hip.h; the cut of
+// a row, the forms and the grids: zc_scvec_plan.h).  The checks behind the pointers, in the header's order.
+static int scvec_args(zc_ctx* ctx, size_t n, size_t terms, const char* who)
+{
+    if (!ctx) return fail(ZC_ERR_BAD_ARG, "null context");
+    if (zc::scv_too_large(n, terms)) return failf(ZC_ERR_BAD_ARG, "%s: n * terms must stay below 2^31", who);
+    return ZC_OK;
+}
+// The launches of `cnt` rows of a sum (b null) or a dot product on slot D: one kernel (the block form, or a row per workgroup), or
+// -- more slices than a workgroup has lanes -- the first kernel into the slot's `scvec` workspace and the one that finishes the rows, both on the slot's stream (a later
+// call's kernels come behind them; a workspace that has to grow is freed first, which waits for the device).
+static int scvec_rows_launch(DevState& D, size_t cnt, size_t terms, const u64* a, const u64* b, bool shared_b, u64* out)
+{
+    const zc::ScvPlan p = zc::scv_plan(cnt, terms);
+    if (p.grid1 >= ((size_t)1 << 31)) return fail(ZC_ERR_BAD_ARG, "more rows than one launch holds");       // rows without terms only: n * terms < 2^31 bounds every other grid
+    const zc::u32 t = (zc::u32)terms, parts = (zc::u32)p.parts, sh = shared_b ? 1u : 0u;
+    if (p.form == zc::SCV_FORM_BLOCK) {
+        if (b) hipLaunchKernelGGL(zc::k_sc_rowdot, dim3((unsigned)p.grid1), dim3(zc::SCV_BLOCK), 0, D.s(), a, b, sh, t, parts, out, cnt);
+        else hipLaunchKernelGGL(zc::k_sc_rowsum, dim3((unsigned)p.grid1), dim3(zc::SCV_BLOCK), 0, D.s(), a, t, parts, out, cnt);
+        return ZC_OK;
+    }
+    if (p.form == zc::SCV_FORM_ROW) {
+        if (b) hipLaunchKernelGGL(zc::k_sc_rowdot_long, dim3((unsigned)p.grid1), dim3(zc::SCV_BLOCK), 0, D.s(), a, b, sh, t, parts, out);
+        else hipLaunchKernelGGL(zc::k_sc_rowsum_long, dim3((unsigned)p.grid1), dim3(zc::SCV_BLOCK), 0, D.s(), a, t, parts, out);
+        return ZC_OK;
+    }
+    if (int rc = D.scvec.grow(p.workspace_bytes)) return rc;
+    zc::u32* const ws = D.scvec.as<zc::u32>();
+    if (b) hipLaunchKernelGGL(zc::k_sc_rowdot_part, dim3((unsigned)p.grid1), dim3(zc::SCV_BLOCK), 0, D.s(), a, b, sh, t, parts, ws);
+    else hipLaunchKernelGGL(zc::k_sc_rowsum_part, dim3((unsigned)p.grid1), dim3(zc::SCV_BLOCK), 0, D.s(), a, t, parts, ws);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(zc::k_sc_rows_finish, dim3((unsigned)p.grid2), dim3(zc::SCV_BLOCK), 0, D.s(), (const zc::u32*)ws, (zc::u32)p.blocks_per_row, out, cnt);
+    return ZC_OK;
+}
+// Rows without terms are zero: nothing of the inputs is read.
+static int scvec_zero_rows(zc_ctx* ctx, uint64_t* out, size_t n)
+{
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, u64* dout) -> int { return scvec_rows_launch(D, cnt, 0, nullptr, nullptr, false, dout); }, ROWS(out, 5));
+}
+int zc_sc_sum_rows(zc_ctx* ctx, const uint64_t* a, size_t terms, uint64_t* out, size_t n)
+{
+    REQUIRE(a);
+    REQUIRE(out);
+    if (int rc = scvec_args(ctx, n, terms, "zc_sc_sum_rows")) return rc;
+    if (terms == 0) return scvec_zero_rows(ctx, out, n);
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) -> int {
+        return scvec_rows_launch(D, cnt, terms, da, nullptr, false, dout);
+    }, ROWS(a, 5 * terms), ROWS(out, 5));
+}
+int zc_sc_dot_rows(zc_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t terms, unsigned flags, uint64_t* out, size_t n)
+{
+    REQUIRE(a);
+    REQUIRE(b);
+    REQUIRE(out);
+    if (flags & ~ZC_SC_DOT_SHARED_B) return fail(ZC_ERR_BAD_ARG, "zc_sc_dot_rows: unknown flag bits");
+    if (int rc = scvec_args(ctx, n, terms, "zc_sc_dot_rows")) return rc;
+    if (n == 0) return ZC_OK;
+    if (terms == 0) return scvec_zero_rows(ctx, out, n);
+    if (!(flags & ZC_SC_DOT_SHARED_B))
+        return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, const u64* db, u64* dout) -> int {
+            return scvec_rows_launch(D, cnt, terms, da, db, false, dout);
+        }, ROWS(a, 5 * terms), ROWS(b, 5 * terms), ROWS(out, 5));
+    // one row of b for every row: it is no buffer of rows, so its place is asked here.  On the device it is used where it lies;
+    // from host memory it goes to each device slot once, on the slot's stream in front of the slot's first kernel (the call holds
+    // the context's lock and ends synchronised, so the copy in `scvec_b` has no other reader).
+    DevState* owner = nullptr;
+    if (int rc = owner_of(ctx, {a, b, out}, "", &owner)) return rc;
+    std::vector<char> sent(ctx->devs.size(), 0);
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* da, u64* dout) -> int {
+        const u64* db = b;
+        if (!owner) {
+            if (!sent[D.slot]) {
+                if (int rc = D.scvec_b.grow(40 * terms)) return rc;
+                HIP_TRY(hipMemcpyAsync(D.scvec_b.as<void>(), b, 40 * terms, hipMemcpyHostToDevice, D.s()));
+                sent[D.slot] = 1;
+            }
+            db = D.scvec_b.as<const u64>();
+        }
+        return scvec_rows_launch(D, cnt, terms, da, db, true, dout);
+    }, ROWS(a, 5 * terms), ROWS(out, 5));
+}
+int zc_sc_powers(zc_ctx* ctx, const uint64_t* x, size_t terms, uint64_t* out, size_t n)
+{
+    REQUIRE(x);
+    REQUIRE(out);
+    if (int rc = scvec_args(ctx, n, terms, "zc_sc_powers")) return rc;
+    if (terms == 0) return ZC_OK;                           // nothing to write
+    return batched(ctx, n, false, [&](DevState& D, size_t cnt, const u64* dx, u64* dout) -> int {
+        const zc::ScvPowPlan p = zc::scv_pow_plan(cnt, terms);
+        hipLaunchKernelGGL(zc::k_sc_powers, dim3((unsigned)p.grid), dim3(zc::SCV_BLOCK), 0, D.s(), dx, (zc::u32)terms, (zc::u32)p.group, dout, cnt);
+        return ZC_OK;
+    }, ROWS(x, 5), ROWS(out, 5 * terms));
 }
 
 // ---- MSM: sum_i k_i * P_i (not in the reference; specified as the reference's own

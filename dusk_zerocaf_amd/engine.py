@@ -21,6 +21,7 @@ from .generators import GeneratorsMixin
 from .hash_batch import HashMixin
 from .point_sums import PointSumsMixin
 from .ristretto_batch import RistrettoBatchMixin
+from .scalar_vec import ScalarVecMixin
 from .scalar_ext import ScalarExtMixin
 from .shared_scalar import SharedScalarMixin
 
@@ -48,7 +49,7 @@ def _one_call(method):
     return locked
 
 
-class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin, SharedScalarMixin, GeneratorsMixin, PointSumsMixin, DlogMixin):
+class Engine(ScalarExtMixin, RistrettoBatchMixin, HashMixin, SharedScalarMixin, GeneratorsMixin, PointSumsMixin, DlogMixin, ScalarVecMixin):
     """One zc_ctx.  `devices=None` = one slot on torch's current device when torch is loaded and sees a GPU; otherwise
     zc_ctx_create(NULL, 0): the calling thread's current HIP device (whatever hipSetDevice chose), read back from the
     context.  The context reads the library's tuning knobs (ZC_* environment variables)

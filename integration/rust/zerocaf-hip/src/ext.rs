@@ -1,7 +1,8 @@
 //! Additive entry points beyond the 0.6 table (`include/zerocaf_hip_ext.h` and `zerocaf_hip_ext_sum.h` / `zerocaf_hip_ext_hash.h`,
 //! which it includes).  The calls with one scalar for a whole batch (`zerocaf_hip_ext_shared.h`, included likewise) and with one
 //! scalar vector for a whole batch (`zerocaf_hip_ext_shared_lincomb.h`) follow; the generator sets (`zerocaf_hip_ext_gens.h`) are
-//! at the end, before the bounded discrete logs, which have a header of their own (`zerocaf_hip_dlog.h`).
+//! at the end, before the bounded discrete logs and the scalar vector ops, which have headers of their own (`zerocaf_hip_dlog.h`,
+//! `zerocaf_hip_scvec.h`).
 //!
 //! `ffi.rs` is the rendering of `zerocaf_hip.h` and stays exactly that; calls declared in the second header are bound here,
 //! with their own `extern "C"` block and a safe wrapper each.
@@ -13,7 +14,7 @@ use zerocaf::ristretto::{CompressedRistretto, RistrettoPoint};
 use zerocaf::scalar::Scalar;
 
 use super::ffi::ZcCtx;
-use super::{bytes32, check, flat_ed, flat_ris, flat_sc, masked, unflat_ed, HipBackend, Result};
+use super::{bytes32, check, flat_ed, flat_ris, flat_sc, masked, unflat_ed, unflat_sc, HipBackend, Result};
 
 extern "C" {
     /// `out32[i] = RistrettoPoint(2 * P_i).compress()`; see `zerocaf_hip_ext.h`.
@@ -317,5 +318,80 @@ impl HipBackend {
             check(unsafe { zc_ris_dlog(self.ctx, id, flat.as_ptr(), bound, m.as_mut_ptr(), found.as_mut_ptr(), std::ptr::null_mut(), n) })?;
         }
         Ok(masked(m, &found))
+    }
+}
+
+// ---- scalar vector ops (`include/zerocaf_hip_scvec.h`, a header beside `zerocaf_hip.h`): row sums, inner products, power rows mod L
+extern "C" {
+    /// `out[i] = sum_j a[i][j] mod L`; `a` is `n * terms * 5` limbs, row-major.
+    pub fn zc_sc_sum_rows(ctx: *mut ZcCtx, a: *const u64, terms: usize, out: *mut u64, n: usize) -> c_int;
+    /// `out[i] = sum_j a[i][j] * b[i][j] mod L`; with `ZC_SC_DOT_SHARED_B`, `b` is one row of `terms * 5` limbs for every row.
+    pub fn zc_sc_dot_rows(ctx: *mut ZcCtx, a: *const u64, b: *const u64, terms: usize, flags: u32, out: *mut u64, n: usize) -> c_int;
+    /// `out[i][j] = x[i]^j mod L` for `j < terms`; `out[i][0] = 1` also for `x = 0`.
+    pub fn zc_sc_powers(ctx: *mut ZcCtx, x: *const u64, terms: usize, out: *mut u64, n: usize) -> c_int;
+}
+
+/// `flags` of `zc_sc_dot_rows`: `b` is one row that every row of `a` uses.
+pub const ZC_SC_DOT_SHARED_B: u32 = 1;
+
+impl HipBackend {
+    /// `a[i][0] + a[i][1] + ...` mod L for every row: rows of one length, any length.  Empty rows give zero.
+    pub fn sc_sum_rows(&self, a: &[Vec<Scalar>]) -> Result<Vec<Scalar>> {
+        let n = a.len();
+        let terms = a.first().map_or(0, |r| r.len());
+        assert!(a.iter().all(|r| r.len() == terms), "rows of one length");
+        let mut fa: Vec<u64> = a.iter().flat_map(|r| flat_sc(r)).collect();
+        fa.resize(fa.len() + 5, 0);
+        let mut out = vec![0u64; n * 5];
+        if n > 0 {
+            check(unsafe { zc_sc_sum_rows(self.ctx, fa.as_ptr(), terms, out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_sc(&out))
+    }
+
+    /// `sum_j a[i][j] * b[i][j]` mod L for every row; `a` and `b` have one shape.
+    pub fn sc_dot_rows(&self, a: &[Vec<Scalar>], b: &[Vec<Scalar>]) -> Result<Vec<Scalar>> {
+        let n = a.len();
+        let terms = a.first().map_or(0, |r| r.len());
+        assert!(b.len() == n && a.iter().chain(b.iter()).all(|r| r.len() == terms), "a and b of one shape");
+        let mut fa: Vec<u64> = a.iter().flat_map(|r| flat_sc(r)).collect();
+        let mut fb: Vec<u64> = b.iter().flat_map(|r| flat_sc(r)).collect();
+        fa.resize(fa.len() + 5, 0);
+        fb.resize(fb.len() + 5, 0);
+        let mut out = vec![0u64; n * 5];
+        if n > 0 {
+            check(unsafe { zc_sc_dot_rows(self.ctx, fa.as_ptr(), fb.as_ptr(), terms, 0, out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_sc(&out))
+    }
+
+    /// `sum_j a[i][j] * b[j]` mod L for every row: one row of `b` for all (weights, Lagrange coefficients, `y^n`).
+    pub fn sc_dot_rows_shared(&self, a: &[Vec<Scalar>], b: &[Scalar]) -> Result<Vec<Scalar>> {
+        let n = a.len();
+        let terms = b.len();
+        assert!(a.iter().all(|r| r.len() == terms), "every row as long as b");
+        let mut fa: Vec<u64> = a.iter().flat_map(|r| flat_sc(r)).collect();
+        let mut fb = flat_sc(b);
+        fa.resize(fa.len() + 5, 0);
+        fb.resize(fb.len() + 5, 0);
+        let mut out = vec![0u64; n * 5];
+        if n > 0 {
+            check(unsafe { zc_sc_dot_rows(self.ctx, fa.as_ptr(), fb.as_ptr(), terms, ZC_SC_DOT_SHARED_B, out.as_mut_ptr(), n) })?;
+        }
+        Ok(unflat_sc(&out))
+    }
+
+    /// `x[i]^0, x[i]^1, ..., x[i]^(terms - 1)` mod L for every `x[i]`; the first is 1 also for `x = 0`.
+    pub fn sc_powers(&self, x: &[Scalar], terms: usize) -> Result<Vec<Vec<Scalar>>> {
+        let n = x.len();
+        let fx = flat_sc(x);
+        let mut out = vec![0u64; n * terms * 5];
+        if n > 0 && terms > 0 {
+            check(unsafe { zc_sc_powers(self.ctx, fx.as_ptr(), terms, out.as_mut_ptr(), n) })?;
+        }
+        if terms == 0 {
+            return Ok(vec![Vec::new(); n]);
+        }
+        Ok(out.chunks_exact(terms * 5).map(unflat_sc).collect())
     }
 }

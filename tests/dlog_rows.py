@@ -14,7 +14,6 @@ scaled by a random Z."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 
@@ -22,12 +21,8 @@ from oracle import pymodel as pm
 from tests import gens_rows as GR
 from tests import point_classes as PC
 from tests import vectors as V
+from tests.emul_build import CSRC
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-EMUL_DIR = os.path.join(HERE, "emul")
-ROCM_INC = "/opt/rocm/include"
 SEED = V.SEED + 0xD106
 COSET4 = 1
 GENERATORS = ("B", "multiple", "mixed")
@@ -233,18 +228,6 @@ def slots_of(records, t):
 # ------------------------------------------------------------------ the host-emulation library (tests/emul/dlog_emul.cpp)
 def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
-
-
-def build_emul(checked=False, src_dir=EMUL_DIR, out_dir=EMUL_DIR, name="libzc_dlog"):
-    """tests/emul/dlog_emul.cpp with g++ -> path of the library, or None without the ROCm headers."""
-    so = os.path.join(out_dir, "%s%s.so" % (name, "_checked" if checked else ""))
-    deps = [os.path.join(src_dir, "dlog_emul.cpp")] + [os.path.join(CSRC, f) for f in ("zc_dlog.hip.h", "zc_dlog_plan.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            return None
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] + (["-DZC_CHECK_BOUNDS"] if checked else []) +
-                              ["-I" + ROCM_INC, "-o", so, deps[0]])
-    return so
 
 
 class Table:

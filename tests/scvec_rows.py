@@ -16,19 +16,14 @@ import functools
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 
 from oracle import pymodel as pm
 from tests import scalar_ext_rows as SR
+from tests.emul_build import CSRC
 
 L, M52, ALL_ONES, HIGH = SR.L, SR.M52, SR.ALL_ONES, SR.HIGH
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-EMUL_DIR = os.path.join(HERE, "emul")
-ROCM_INC = "/opt/rocm/include"
 SEED = 2300
 TOPBIT = 249
 WORST = (1 << 260) - 1
@@ -209,18 +204,6 @@ def label(op, family, n, terms):
 
 
 # ------------------------------------------------------------------ the emulation
-def build_emul(checked=False, src_dir=EMUL_DIR, out_dir=EMUL_DIR, name="libzc_scvec", csrc=CSRC):
-    """tests/emul/scvec_emul.cpp with g++ -> path of the library, or None without the ROCm headers."""
-    so = os.path.join(out_dir, "%s%s.so" % (name, "_checked" if checked else ""))
-    deps = [os.path.join(src_dir, "scvec_emul.cpp")] + [os.path.join(csrc, f) for f in ("zc_scvec.hip.h", "zc_scvec_plan.h", "zc_arith.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            return None
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-fno-gnu-unique", "-Wl,-Bsymbolic"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
-    return so
-
-
 GUARD = 3                                           # rows in front of and behind every output, which must stay as they were
 FILL = 0xA5A5A5A5A5A5A5A5
 

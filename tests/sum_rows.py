@@ -8,8 +8,6 @@ every longer one.  By i mod 8: 1 one point repeated, 2 P followed by -P, 7 all i
 walk through the pool.  The wire rows are encodings of doubled pool points (always decodable) and the zero encoding; rows with
 i mod 8 in (1, 3, 6) carry an undecodable encoding in the first, a middle and the last term position."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -171,24 +169,6 @@ def want_wire(oracle, n, terms):
 # ------------------------------------------------------------------ the host-emulation library (tests/emul/sum_rows_emul.cpp)
 def _p(a):
     return C.c_void_p(a.ctypes.data)
-
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(os.path.dirname(HERE), "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
-
-
-def build_emul(checked=False):
-    """The emulation library, rebuilt when a source is newer: the path, or None where the ROCm headers are missing."""
-    so = os.path.join(EMUL_DIR, "libzc_sum_rows%s.so" % ("_checked" if checked else ""))
-    deps = [os.path.join(EMUL_DIR, "sum_rows_emul.cpp")] + [os.path.join(CSRC, f) for f in ("zc_sum.hip.h", "zc_sum_plan.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            return None
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] + (["-DZC_CHECK_BOUNDS"] if checked else []) +
-                              ["-I" + ROCM_INC, "-o", so, deps[0]])
-    return so
 
 
 class Emul:

@@ -5,17 +5,14 @@ algorithms before any GPU time is spent; it is not a CPU fallback (nothing in
 dusk_zerocaf_amd/ can reach it)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import hostile_rows as H
 from tests import vectors as V
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL_DIR = os.path.join(HERE, "emul")
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
@@ -24,18 +21,9 @@ def emul(request):
     scheme (limb ranges of multiplier inputs, subtrahends below the 4N bias, ...) aborts when violated."""
     checked = request.param == "checked"
     # ZC_EMUL_SANITIZE (tests/test_sanitizers.py): the same build under AddressSanitizer + UBSan, no recovery
-    san = bool(os.environ.get("ZC_EMUL_SANITIZE"))
-    so = os.path.join(EMUL_DIR, "libzc_emul%s%s.so" % ("_san" if san else "", "_checked" if checked else ""))
-    src = os.path.join(EMUL_DIR, "emul.cpp")
-    csrc = os.path.join(os.path.dirname(HERE), "dusk_zerocaf_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        inc = "/opt/rocm/include"
-        if not os.path.isdir(inc):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]) +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + inc, "-o", so, src])
+    so = EB.library("emul.cpp", checked=checked, sanitize=bool(os.environ.get("ZC_EMUL_SANITIZE")))
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.zc_checked = checked
     return lib

@@ -5,21 +5,20 @@ build, sliced search and both forms against the planted truth of tests/dlog_rows
 arbitrary giant steps.  The sanitizer run is a stand-alone program (tests/emul/dlog_san.cpp) replaying a vector file as a child
 process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import dlog_rows as DR
+from tests import emul_build as EB
 
 PC, GR = DR.PC, DR.GR
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    so = DR.build_emul(request.param == "checked")
+    so = EB.library("dlog_emul.cpp", checked=request.param == "checked")
     if so is None:
         pytest.skip("ROCm headers not present")
     return DR.Emul(C.CDLL(so))
@@ -161,11 +160,7 @@ def test_the_whole_tier_passes_as_the_mutant_test_runs_it(emul, oracle):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
     """tests/emul/dlog_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all: setup block, records, slots, rows and
     outputs in heap blocks of exactly their size; its exit status is the verdict."""
-    if not os.path.isdir(DR.ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "dlog_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + DR.ROCM_INC, "-o", exe, os.path.join(DR.EMUL_DIR, "dlog_san.cpp")])
+    exe = EB.sanitizer_program("dlog_san.cpp", tmp_path)
     parts, rows = [], 0
     R = DR.ed_rows(oracle, "mixed", 4, 0)
     pts = np.concatenate([R["points"][:40], DR.hostile_points(oracle)])
@@ -177,15 +172,7 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
                  b"".join(W[k].astype(np.uint64).tobytes() for k in ("m", "found", "ok")))
     rows += len(W["enc"])
     blob = b"".join(parts) + struct.pack("<Q", 2)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "2 records, %d rows match" % rows in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "2 records, %d rows match" % rows)
     bad = bytearray(blob)
     bad[-16] ^= 1                                                                       # the last row's expected ok
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "record 1: row %d:" % (len(W["enc"]) - 1) in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "record 1: row %d:" % (len(W["enc"]) - 1))

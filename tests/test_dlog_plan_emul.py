@@ -3,25 +3,23 @@ tests/emul/dlog_plan_emul.cpp -- no HIP header) against a Python restatement and
 every (bound, table_bits) edge, the slot array's layout, and the refusal of a record that occurs twice."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import dlog_rows as DR
+from tests import emul_build as EB
+from tests.emul_build import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMUL_DIR = os.path.join(ROOT, "tests", "emul")
 EMPTY = DR.EMPTY
 ULL = C.c_ulonglong
 
 
 @pytest.fixture(scope="module")
 def plan():
-    so = os.path.join(EMUL_DIR, "libzc_dlog_plan.so")
-    deps = [os.path.join(EMUL_DIR, "dlog_plan_emul.cpp"), os.path.join(DR.CSRC, "zc_dlog_plan.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-Wall", "-Werror", "-o", so, deps[0]])
+    so = EB.library("dlog_plan_emul.cpp", flags=EB.STRICT)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     for name in ("plan_dlog_steps", "plan_dlog_launches", "plan_dlog_offset_word", "plan_dlog_home"):
         getattr(lib, name).restype = ULL

@@ -4,36 +4,25 @@ Python integers; the composed check runs the addition formulas that call the rou
 point class.  The sanitizer run is a stand-alone program (tests/emul/fe_muld_san.cpp) replaying a vector file as a child
 process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import fe_muld_rows as FM
 from tests import point_classes as PC
 from tests import vectors as V
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 FORMS = {0: "ptm_add", 1: "ptm_add ilp", 2: "pt_add", 3: "pt_add ilp", 4: "pt_add_plain", 5: "pt_add_plain ilp"}
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_fe_muld%s.so" % ("_checked" if checked else ""))
-    deps = [os.path.join(EMUL_DIR, "fe_muld_emul.cpp")] + [os.path.join(CSRC, f) for f in ("zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("fe_muld_emul.cpp", checked=request.param == "checked")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     return C.CDLL(so)
 
 
@@ -88,11 +77,7 @@ def test_addition_formulas_match_the_oracle(emul, pairs, form):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle, pairs):
     """tests/emul/fe_muld_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all and the bounds assertions on the
     named inputs, 4 000 random ones and the point pairs in every form; its exit status is the verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "fe_muld_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DZC_CHECK_BOUNDS",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "fe_muld_san.cpp")])
+    exe = EB.sanitizer_program("fe_muld_san.cpp", tmp_path, checked=True)
     names, x, want, _ = FM.inputs(oracle)
     n = len(names) - FM.N_RANDOM + 4000
     blob = struct.pack("<QQ", 1, n) + np.ascontiguousarray(x[:n]).tobytes() + np.ascontiguousarray(want[:n]).tobytes()
@@ -100,16 +85,8 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle, pairs):
     for form in sorted(FORMS):
         blob += struct.pack("<QQ", 2 + form, 512) + p[-700:-188].tobytes() + q[-700:-188].tobytes() + sums[-700:-188].tobytes()
     blob += struct.pack("<QQ", 0, 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "rows match" in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "rows match")
     # the verdict is a real one: one expected limb changed and the program says so
     bad = bytearray(blob)
     bad[16 + 36 * n + 40 * 3 + 8] ^= 1                                                     # limb 1 of row 3 of the first record's expected values
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "row 3 word 1" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "row 3 word 1")

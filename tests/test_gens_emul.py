@@ -10,31 +10,22 @@ import hashlib
 import json
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import emul_build as EB
 from tests import gens_rows as GR
+from tests.emul_build import HERE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
-N = GR.POOL + 37                                     # rows repeat from POOL on
+N =GR.POOL + 37                                     # rows repeat from POOL on
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_gens%s.so" % ("_checked" if checked else ""))
-    deps = [os.path.join(EMUL_DIR, "gens_emul.cpp")] + [os.path.join(CSRC, f) for f in ("zc_gens.hip.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("gens_emul.cpp", checked=request.param == "checked")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     return GR.Emul(C.CDLL(so))
 
 
@@ -144,26 +135,14 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
     """tests/emul/gens_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all: tables in heap blocks of exactly
     33 * 128 * 128 * count bytes, every scalar of the pool in the first and in the last term position; its exit status is the
     verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "gens_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "gens_san.cpp")])
+    exe = EB.sanitizer_program("gens_san.cpp", tmp_path)
     parts, rows = [], 0
     for count in (1, 3):
         G, K, enc = GR.generators(oracle, count), GR.scalars(count), GR.want(oracle, count)[1]
         parts.append(struct.pack("<2Q", count, len(K)) + GR.with_true_t(oracle, G).tobytes() + K.tobytes() + np.ascontiguousarray(enc).tobytes())
         rows += len(K)
     blob = b"".join(parts) + struct.pack("<Q", 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "2 records, %d rows match" % rows in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "2 records, %d rows match" % rows)
     bad = bytearray(blob)
     bad[-9] ^= 1                                                                        # the last byte of the last expected encoding
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "record 1: row %d: word 3" % (GR.POOL - 1) in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "record 1: row %d: word 3" % (GR.POOL - 1))

@@ -6,22 +6,15 @@ from the copy with g++ (no sanitizer, no bounds assertions) and GR.failures run 
 families `killers` names must be among the failures (where `spared` names some, they must pass).  Every planted defect stays
 inside the tables the emulation allocates.  The unmutated copy passes, and every `old` text occurs exactly once in its header.
 Nothing is written inside the repository tree."""
-import concurrent.futures
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import gens_rows as GR
+from tests.emul_build import CSRC
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-EMUL_DIR = os.path.join(HERE, "emul")
-ROCM_INC = "/opt/rocm/include"
 GENS, CURVE = "zc_gens.hip.h", "zc_curve.hip.h"
 ROWS = ["ed", "wire"]
 
@@ -45,44 +38,14 @@ MUTANTS = [
 BY_NAME = {m["name"]: m for m in MUTANTS}
 
 
-def make_copy(where, m=None):
-    csrc = os.path.join(where, "dusk_zerocaf_amd", "csrc")
-    emul = os.path.join(where, "tests", "emul")
-    os.makedirs(csrc)
-    os.makedirs(emul)
-    for f in glob.glob(os.path.join(CSRC, "*.h")):
-        shutil.copy(f, csrc)
-    shutil.copy(os.path.join(EMUL_DIR, "gens_emul.cpp"), emul)
-    if m is not None:
-        path = os.path.join(csrc, m["header"])
-        with open(path) as f:
-            text = f.read()
-        assert text.count(m["old"]) == 1, m["name"]
-        with open(path, "w") as f:
-            f.write(text.replace(m["old"], m["new"]))
-    so = os.path.join(where, "libzc_gens.so")
-    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-fno-gnu-unique", "-Wl,-Bsymbolic",
-                           "-I" + ROCM_INC, "-o", so, os.path.join(emul, "gens_emul.cpp")])
-    return so
-
-
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    names = [None] + [m["name"] for m in MUTANTS]
-    dirs = [str(tmp_path_factory.mktemp(n or "unmutated")) for n in names]
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-        out = dict(zip(names, pool.map(lambda a: make_copy(a[0], BY_NAME.get(a[1])), zip(dirs, names))))
-    assert not any(p.startswith(ROOT + os.sep) for p in out.values())
-    return out
+    return EB.mutant_builds(tmp_path_factory, MUTANTS, "gens_emul.cpp")
 
 
 def test_catalogue_is_sound():
-    assert len(BY_NAME) == len(MUTANTS) and 4 <= len(MUTANTS)
-    for m in MUTANTS:
-        text = open(os.path.join(CSRC, m["header"])).read()
-        assert text.count(m["old"]) == 1 and m["old"] != m["new"], m["name"]
+    EB.catalogue_is_sound(MUTANTS)
+    assert 4 <= len(MUTANTS)
     gens = open(os.path.join(CSRC, GENS)).read()
     curve = open(os.path.join(CSRC, CURVE)).read()
     # the window loop that is cut short is the generalised column builder's
@@ -99,13 +62,4 @@ def test_unmutated_copy_passes(built, oracle):
 
 @pytest.mark.parametrize("name", [m["name"] for m in MUTANTS])
 def test_planted_defect_is_killed(built, oracle, name):
-    m = BY_NAME[name]
-    failed = GR.failures(C.CDLL(built[name]), oracle)
-    assert failed != [], "%s survived" % name
-    families = {f.rsplit(" [", 1)[0] for f in failed}
-    assert set(m["killers"]) <= families, (name, sorted(families))
-    assert not set(m.get("spared", [])) & families, (name, sorted(families))
-    for case in m.get("cases", []):
-        assert case in failed, (name, case, failed)
-    for case in m.get("spared_cases", []):
-        assert case not in failed, (name, case, failed)
+    EB.assert_killed(BY_NAME[name], GR.failures(C.CDLL(built[name]), oracle))

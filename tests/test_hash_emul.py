@@ -6,34 +6,22 @@ The sanitizer run is a stand-alone program (tests/emul/hash_san.cpp) replaying a
 sanitized is loaded here."""
 import ctypes as C
 import hashlib
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import emul_build as EB
 from tests import hash_rows as HR
 from tests import scalar_ext_rows as S
 from tests import vectors as V
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
-
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_hash%s.so" % ("_checked" if checked else ""))
-    deps = [os.path.join(EMUL_DIR, "hash_emul.cpp")] + [os.path.join(CSRC, f) for f in ("zc_hash.hip.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("hash_emul.cpp", checked=request.param == "checked")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     return C.CDLL(so)
 
 
@@ -184,11 +172,7 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
     """tests/emul/hash_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all and the bounds assertions, on a
     vector file of digests (both forms, parts ending with their heap block, aligned and odd), scalars and points; its exit
     status is the verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "hash_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DZC_CHECK_BOUNDS",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "hash_san.cpp")])
+    exe = EB.sanitizer_program("hash_san.cpp", tmp_path, checked=True)
     blob, first = b"", None
     cases = [(b"", [t]) for t in (1, 7, 8, 111, 112, 119, 120, 127, 128, 129, 239, 240, 257)] + HR.kill_cases()[260:] + [(b"", [HR.MAX_ROW_BYTES])]
     for ci, (prefix, lens) in enumerate(cases):
@@ -203,18 +187,10 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
         if ci % 4 == 0:
             blob += _record(2, parts, prefix, HR.points_of(dig))
     blob += struct.pack("<Q", 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "rows match" in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "rows match")
     # the verdict is a real one: one expected byte changed and the program says so
     bad = bytearray(blob)
     parts, dig = first
     assert parts[0].shape == (5, 1)
     bad[7 * 8 + 0 + 8 + 64 * 3 + 9] ^= 1           # header (6 words + 1 length), empty prefix, the part (5 bytes padded to 8): byte 9 of row 3
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "record 0 (op 0): row 3 byte 9" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "record 0 (op 0): row 3 byte 9")

@@ -6,22 +6,15 @@ built from the copy with g++ (no sanitizer, no bounds assertions) and HR.failure
 where `killers` names families of vectors, those must be among the failures (and where `spared` names some, they must pass: a
 defect of one reader form leaves the other alone).  The unmutated copy passes, and every `old` text occurs exactly once in the
 header.  Nothing is written inside the repository tree."""
-import concurrent.futures
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import hash_rows as HR
+from tests.emul_build import CSRC
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-EMUL_DIR = os.path.join(HERE, "emul")
-ROCM_INC = "/opt/rocm/include"
 HASH = "zc_hash.hip.h"
 CH_MAJ = ("ZC_DI u64 sha512_ch(u64 e, u64 f, u64 g) { return g ^ (e & (f ^ g)); }\n"
           "ZC_DI u64 sha512_maj(u64 a, u64 b, u64 c) { return (a & b) | (c & (a | b)); }")
@@ -49,44 +42,14 @@ MUTANTS = [
 BY_NAME = {m["name"]: m for m in MUTANTS}
 
 
-def make_copy(where, m=None):
-    csrc = os.path.join(where, "dusk_zerocaf_amd", "csrc")
-    emul = os.path.join(where, "tests", "emul")
-    os.makedirs(csrc)
-    os.makedirs(emul)
-    for f in glob.glob(os.path.join(CSRC, "*.h")):
-        shutil.copy(f, csrc)
-    shutil.copy(os.path.join(EMUL_DIR, "hash_emul.cpp"), emul)
-    if m is not None:
-        path = os.path.join(csrc, HASH)
-        with open(path) as f:
-            text = f.read()
-        assert text.count(m["old"]) == 1, m["name"]
-        with open(path, "w") as f:
-            f.write(text.replace(m["old"], m["new"]))
-    so = os.path.join(where, "libzc_hash.so")
-    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-fno-gnu-unique", "-Wl,-Bsymbolic",
-                           "-I" + ROCM_INC, "-o", so, os.path.join(emul, "hash_emul.cpp")])
-    return so
-
-
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    names = [None] + [m["name"] for m in MUTANTS]
-    dirs = [str(tmp_path_factory.mktemp(n or "unmutated")) for n in names]
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-        out = dict(zip(names, pool.map(lambda a: make_copy(a[0], BY_NAME.get(a[1])), zip(dirs, names))))
-    assert not any(p.startswith(ROOT + os.sep) for p in out.values())
-    return out
+    return EB.mutant_builds(tmp_path_factory, MUTANTS, "hash_emul.cpp", headers=HASH)
 
 
 def test_catalogue_is_sound():
-    assert len(BY_NAME) == len(MUTANTS)
+    EB.catalogue_is_sound(MUTANTS, headers=HASH)
     text = open(os.path.join(CSRC, HASH)).read()
-    for m in MUTANTS:
-        assert text.count(m["old"]) == 1 and m["old"] != m["new"], m["name"]
     # the four rotation entries sit in the four functions they name, the constant is the table's 79th
     for fn, old in (("sha512_Sigma0", "rotr64<28>(x)"), ("sha512_Sigma1", "rotr64<14>(x)"), ("sha512_sigma0", "rotr64<1>(x)"), ("sha512_sigma1", "rotr64<19>(x)")):
         line = next(l for l in text.split("\n") if l.startswith("ZC_DI u64 %s(" % fn))
@@ -102,9 +65,6 @@ def test_unmutated_copy_passes(built, oracle):
 def test_planted_defect_is_killed(built, oracle, name):
     m = BY_NAME[name]
     failed = HR.failures(C.CDLL(built[name]), oracle)
-    assert failed != [], "%s survived" % name
-    families = {f.rsplit(" [", 1)[0] for f in failed}
-    assert set(m["killers"]) <= families, (name, sorted(families))
-    assert not set(m.get("spared", [])) & families, (name, sorted(families))
-    for case in m.get("cases", []):
+    EB.assert_killed({k: v for k, v in m.items() if k != "cases"}, failed)
+    for case in m.get("cases", []):                                                      # here a case names the vector, whichever family fails on it
         assert any(f.endswith("[%s]" % case) for f in failed), (name, case)

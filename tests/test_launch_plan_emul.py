@@ -23,18 +23,16 @@ import ctypes as C
 import json
 import os
 import struct
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import entry_table as T
 from tests import kill_vectors as KV
+from tests.emul_build import CSRC, HERE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
 TABLE = os.path.join(HERE, "golden", "launch_plan_table.json")
-HEADER = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc", "zc_launch_plan.h")
+HEADER = os.path.join(CSRC, "zc_launch_plan.h")
 
 HOST_CHUNK, ELEMENTWISE, STRICT, INVERSION, RING, LINCOMB, HASH = range(7)
 KINDS = {
@@ -110,11 +108,9 @@ def grid():
 
 
 def build_emul():
-    so = os.path.join(EMUL_DIR, "libzc_launch_plan.so")
-    src = os.path.join(EMUL_DIR, "launch_plan_emul.cpp")
-    deps = [src, HEADER, os.path.join(os.path.dirname(HEADER), "zc_msm_plan.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O2", "-fPIC", "-shared", "-o", so, src])
+    so = EB.library("launch_plan_emul.cpp", flags=EB.STRICT)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     return load(so)
 
 
@@ -237,24 +233,14 @@ def vector_file(rows):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, table):
     """tests/emul/launch_plan_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all on the whole table (the shifts,
     casts and products at 2^32 and 2^33 rows among it); its exit status is the verdict."""
-    exe = str(tmp_path / "launch_plan_san")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-o", exe, os.path.join(EMUL_DIR, "launch_plan_san.cpp")])
+    exe = EB.sanitizer_program("launch_plan_san.cpp", tmp_path, flags=EB.STRICT)
     rows = table["rows"]
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(vector_file(rows))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "%d cases match" % len(rows) in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, vector_file(rows), tmp_path, "vectors.bin"), "%d cases match" % len(rows))
     # the verdict is a real one: one expected field changed and the program says so
     i = next(j for j, r in enumerate(rows) if r[0] == STRICT)
     bad = [list(r) for r in rows]
     bad[i] = [rows[i][0], rows[i][1], rows[i][2][:3] + [rows[i][2][3] + 1]]
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(vector_file(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "case %d (kind %d): field 3" % (i, STRICT) in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, vector_file(bad), tmp_path, "wrong.bin"), "case %d (kind %d): field 3" % (i, STRICT))
 
 
 def write_table(lib, path):

@@ -13,30 +13,20 @@ import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import lincomb_rows as R
 from tests import vectors as V
+from tests.emul_build import EMUL_DIR, ROOT
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
 TERMS = [1, 2, 3, 4, 5, 8]
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
     checked = request.param == "checked"
-    san = bool(os.environ.get("ZC_EMUL_SANITIZE"))
-    so = os.path.join(EMUL_DIR, "libzc_lincomb%s%s.so" % ("_san" if san else "", "_checked" if checked else ""))
-    src = os.path.join(EMUL_DIR, "lincomb_emul.cpp")
-    csrc = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        inc = "/opt/rocm/include"
-        if not os.path.isdir(inc):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]) +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + inc, "-o", so, src])
+    so = EB.library("lincomb_emul.cpp", checked=checked, sanitize=bool(os.environ.get("ZC_EMUL_SANITIZE")))
+    if so is None:
+        pytest.skip("ROCm headers not present")
     return C.CDLL(so)
 
 

@@ -20,9 +20,9 @@ import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
+from tests import emul_build as EB
+from tests.emul_build import EMUL_DIR, HERE, ROOT
+
 TABLE = os.path.join(HERE, "golden", "msm_plan_table.json")
 
 FIELDS = (["limit", "buckets", "c", "W", "affine", "rec_bytes", "T", "TE", "seg", "m", "nb", "nseg", "nl0", "G"] +
@@ -102,13 +102,9 @@ def grid():
 
 
 def build_emul():
-    san = bool(os.environ.get("ZC_EMUL_SANITIZE"))
-    so = os.path.join(EMUL_DIR, "libzc_msm_plan%s.so" % ("_san" if san else ""))
-    src = os.path.join(EMUL_DIR, "msm_plan_emul.cpp")
-    deps = [src, os.path.join(ROOT, "dusk_zerocaf_amd", "csrc", "zc_msm_plan.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared"] +
-                              (["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]) + ["-o", so, src])
+    so = EB.library("msm_plan_emul.cpp", sanitize=bool(os.environ.get("ZC_EMUL_SANITIZE")), flags=EB.STRICT)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.emul_msm_plan.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     assert lib.emul_msm_plan_fields() == len(FIELDS)

@@ -6,23 +6,16 @@ with g++ (as the other emulation fixtures build theirs, no sanitizer), loaded wi
 least one comparison must fail.  The unmutated copy must pass every family, every `old` text must occur exactly once in its
 header, and the canary (fe_carry stopping at limb 7) must be killed.  Nothing is written inside the repository tree; the
 builds run on a thread pool of at most 16."""
-import concurrent.futures
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import kill_vectors as KV
 from tests import mutants as M
+from tests.emul_build import HERE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-EMUL_DIR = os.path.join(HERE, "emul")
-ROCM_INC = "/opt/rocm/include"
 HEADERS = {M.ARITH: "zc_arith.hip.h", M.CURVE: "zc_curve.hip.h"}
 BY_NAME = {m["name"]: m for m in M.MUTANTS}
 
@@ -39,48 +32,10 @@ def families_of(m):
     return m["survives"] if "equivalent" in m else (m["family"],)
 
 
-def make_copy(where, m=None):
-    """The layout the emulation sources include through, with the entry's replacement applied to the copied header."""
-    csrc = os.path.join(where, "dusk_zerocaf_amd", "csrc")
-    emul = os.path.join(where, "tests", "emul")
-    os.makedirs(csrc)
-    os.makedirs(emul)
-    for f in glob.glob(os.path.join(CSRC, "*.h")):
-        shutil.copy(f, csrc)
-    for f in glob.glob(os.path.join(EMUL_DIR, "*.cpp")):
-        shutil.copy(f, emul)
-    if m is not None:
-        path = os.path.join(csrc, HEADERS[m["header"]])
-        with open(path) as f:
-            text = f.read()
-        assert text.count(m["old"]) == 1, m["name"]
-        with open(path, "w") as f:
-            f.write(text.replace(m["old"], m["new"]))
-    return where
-
-
-def build(where, lib):
-    so = os.path.join(where, "lib_%s.so" % lib)
-    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-fno-gnu-unique", "-Wl,-Bsymbolic",
-                           "-I" + ROCM_INC, "-o", so, os.path.join(where, "tests", "emul", KV.LIBS[lib])])
-    return so
-
-
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    """{entry name or None (the unmutated copy): {library: path}}, everything built up front on the pool."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    jobs = [(None, lib) for lib in KV.LIBS]
-    for m in M.MUTANTS:
-        jobs += [(m["name"], lib) for lib in sorted({KV.FAMILIES[f].lib for f in families_of(m)})]
-    dirs = {name: make_copy(str(tmp_path_factory.mktemp(name or "unmutated")), BY_NAME.get(name)) for name in {j[0] for j in jobs}}
-    out = {name: {} for name in dirs}
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-        for (name, lib), so in zip(jobs, pool.map(lambda j: build(dirs[j[0]], j[1]), jobs)):
-            out[name][lib] = so
-    assert not any(p.startswith(ROOT + os.sep) for libs in out.values() for p in libs.values())
-    return out
+    """{entry name or None (the unmutated copy): {library: path}}: per entry the libraries its families load."""
+    return EB.mutant_builds(tmp_path_factory, M.MUTANTS, KV.LIBS, headers=HEADERS, needs=lambda m: sorted({KV.FAMILIES[f].lib for f in families_of(m)}), workers=16)
 
 
 def failures(built, name, family):
@@ -89,12 +44,10 @@ def failures(built, name, family):
 
 
 def test_catalogue_is_sound():
-    names = [m["name"] for m in M.MUTANTS]
-    assert len(names) == len(set(names)) and len(names) >= 40
-    headers = {k: open(os.path.join(CSRC, v)).read() for k, v in HEADERS.items()}
+    EB.catalogue_is_sound(M.MUTANTS, headers=HEADERS)
+    assert len(M.MUTANTS) >= 40
     for m in M.MUTANTS:
-        assert headers[m["header"]].count(m["old"]) == 1, "%s: `old` occurs %d times" % (m["name"], headers[m["header"]].count(m["old"]))
-        assert m["old"] != m["new"] and all(f in KV.FAMILIES for f in families_of(m)), m["name"]
+        assert all(f in KV.FAMILIES for f in families_of(m)), m["name"]
         assert ("equivalent" in m) != ("family" in m) and ("equivalent" not in m or len(m["equivalent"]) > 80), m["name"]
     kinds = [kind(m) for m in M.MUTANTS]
     assert kinds.count("equivalent") <= 0.15 * len(kinds), kinds.count("equivalent")

@@ -4,42 +4,28 @@ ris_double_compress_chunk), built for the host by tests/emul/ris_dac_emul.cpp in
 on Python integers against oracle/pymodel.py, so both oracles are on record.  The sanitizer run is a stand-alone program
 (tests/emul/ris_dac_san.cpp) replaying a vector file as a child process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import hostile_rows as H
 from tests import point_classes as PC
 from tests import vectors as V
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 CHUNKS = [1, 2, 3, 16, 64]
 SEED = V.SEED + 0xDAC0
-
-
-def _deps(*srcs):
-    return [os.path.join(EMUL_DIR, s) for s in srcs] + [os.path.join(CSRC, f) for f in ("zc_ris_batch.hip.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
     checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_ris_dac%s.so" % ("_checked" if checked else ""))
-    deps = _deps("ris_dac_emul.cpp")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("ris_dac_emul.cpp", checked=checked)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.checked = checked
     return lib
@@ -184,12 +170,8 @@ def _record(op, n, c, rows, want):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, catalogue):
     """tests/emul/ris_dac_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all and the bounds assertions, on a
     vector file with the catalogue and planted hostile rows for every chunk length; its exit status is the verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
+    exe = EB.sanitizer_program("ris_dac_san.cpp", tmp_path, checked=True)
     rows, names, want = catalogue
-    exe = str(tmp_path / "ris_dac_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DZC_CHECK_BOUNDS",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "ris_dac_san.cpp")])
     blob = _record(1, 96, 0, rows[:96], want[:96])
     for c in CHUNKS:
         n = 10 * max(c, 8) + 3
@@ -200,16 +182,8 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, catalogue):
         for op in (2, 3):
             blob += _record(op, n, c, a, w)
     blob += struct.pack("<QQQ", 0, 0, 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "rows match" in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "rows match")
     # the verdict is a real one: one expected byte changed and the program says so
     bad = bytearray(blob)
     bad[24 + 160 * 96 + 32 * 3 + 5] ^= 1                                                   # byte 5 of row 3 of the first record's encodings
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "row 3 byte 5" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "row 3 byte 5")

@@ -5,46 +5,31 @@ reduction, ris_sum_store_basepoint), built for the host by tests/emul/ris_sum_em
 batch.  The sanitizer run is a stand-alone program (tests/emul/ris_sum_san.cpp) replaying a vector file as a child process:
 nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import ris_lincomb_rows as RR
 from tests import ris_sum_rows as RS
 from tests import scalar_ext_rows as SX
 from tests import vectors as V
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 SEED = V.SEED + 0x5A70
 L = pm.L
 BLOCK, PER_LANE, MAX_BLOCKS = 64, 4, 3            # the emulator's reduction geometry: a workgroup's span is 256 rows
 VP = C.c_void_p
 
 
-def _deps(*srcs):
-    return [os.path.join(EMUL_DIR, s) for s in srcs] + [os.path.join(CSRC, f) for f in ("zc_ris_batch.hip.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h",
-                                                                                         "zc_msm_plan.h")]
-
-
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
     checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_ris_sum%s.so" % ("_checked" if checked else ""))
-    deps = _deps("ris_sum_emul.cpp")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("ris_sum_emul.cpp", checked=checked)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.checked = checked
     return lib
@@ -183,11 +168,7 @@ def _record(E, K, KB, Z, want_p, want_s, want_ok):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
     """tests/emul/ris_sum_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all and the bounds assertions, on a
     vector file of batches with and without base term and weights; its exit status is the verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "ris_sum_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DZC_CHECK_BOUNDS",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "ris_sum_san.cpp")])
+    exe = EB.sanitizer_program("ris_sum_san.cpp", tmp_path, checked=True)
     blob, first = b"", None
     for n, t, base, weights in ((1, 1, False, False), (3, 2, True, True), (65, 1, True, False), (300, 2, True, True), (20, 7, False, True)):
         E, K, KB, Z, _ = batch(oracle, n, t, SEED + 900 + n)
@@ -205,16 +186,8 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
         first = first or len(blob) + 32 + E.nbytes + K.nbytes + (KB.nbytes if base else 0) + (Z.nbytes if weights else 0)
         blob += _record(E, K, KB, Z, want_p, SX.rows(want_s), ok)
     blob += struct.pack("<QQQQ", 0, 0, 0, 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "rows match" in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "rows match")
     # the verdict is a real one: one expected byte changed and the program says so
     bad = bytearray(blob)
     bad[first + 8] ^= 1                                                                  # in X of the first record's first expected point
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "points" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "points")

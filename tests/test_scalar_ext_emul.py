@@ -4,39 +4,24 @@ host by tests/emul/scalar_ext_emul.cpp in the plain and the bounds-asserting (-D
 reference, so every row is compared with Python integers (tests/scalar_ext_rows.py).  The sanitizer run is a stand-alone
 program (tests/emul/scalar_ext_san.cpp) replaying a vector file as a child process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import emul_build as EB
 from tests import hostile_rows as H
 from tests import scalar_ext_rows as S
 from tests import vectors as V
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 CHUNKS = [1, 2, 3, 16, 64]
-
-
-def _deps(*srcs):
-    return [os.path.join(EMUL_DIR, s) for s in srcs] + [os.path.join(CSRC, f) for f in ("zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_scalar_ext%s.so" % ("_checked" if checked else ""))
-    deps = _deps("scalar_ext_emul.cpp")
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("scalar_ext_emul.cpp", checked=request.param == "checked")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     return C.CDLL(so)
 
 
@@ -171,11 +156,7 @@ def _record(op, n, c, *arrays):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path):
     """tests/emul/scalar_ext_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all and the bounds assertions, on a
     vector file with inputs and expected outputs of every family above; its exit status is the verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "scalar_ext_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DZC_CHECK_BOUNDS",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "scalar_ext_san.cpp")])
+    exe = EB.sanitizer_program("scalar_ext_san.cpp", tmp_path, checked=True)
     blob = b""
     for width, op in ((64, 1), (32, 2)):
         vals = S.reduction_values(width, 512, V.SEED + 0x5C31 + width)
@@ -193,16 +174,8 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path):
         for op in (5, 6):
             blob += _record(op, n, ci, a, *S.invert_expected(a))
     blob += struct.pack("<QQQ", 0, 0, 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "rows match" in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "rows match")
     # the verdict is a real one: one expected limb changed and the program says so
     bad = bytearray(blob)
     bad[24 + 64 * (len(S.reduction_values(64, 512, 0))) + 5 * 8 * 3] ^= 1         # limb 0 of row 3 of the first record's expected values
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "row 3 limb 0" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "row 3 limb 0")

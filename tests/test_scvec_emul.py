@@ -5,14 +5,13 @@ tests/scvec_rows.py against Python integers; the column and fold bounds at the w
 call can produce; results that depend on the row alone.  The sanitizer run is a stand-alone program (tests/emul/scvec_san.cpp)
 replaying a vector file as a child process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import scvec_rows as R
 
 L = R.L
@@ -20,7 +19,7 @@ L = R.L
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    so = R.build_emul(request.param == "checked")
+    so = EB.library("scvec_emul.cpp", checked=request.param == "checked")
     if so is None:
         pytest.skip("ROCm headers not present")
     return R.Emul(C.CDLL(so))
@@ -91,11 +90,7 @@ def test_the_whole_tier_passes_as_the_mutant_test_runs_it(emul):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path):
     """tests/emul/scvec_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all: inputs and outputs in heap blocks of
     exactly their size; its exit status is the verdict."""
-    if not os.path.isdir(R.ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "scvec_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + R.ROCM_INC, "-o", exe, os.path.join(R.EMUL_DIR, "scvec_san.cpp")])
+    exe = EB.sanitizer_program("scvec_san.cpp", tmp_path)
     parts, rows = [], 0
     for key in [("sum", "edges", 65, 7), ("sum", "random", 1, 32769), ("dot", "edges", 63, 3), ("dot", "worst", 3, 1025), ("dot", "random", 3, 49153), ("dot_shared", "edges", 257, 33),
                 ("dot_shared", "random", 3, 1025), ("sum", "random", 64, 0), ("powers", "bases", 65, 33), ("powers", "bases", 3, 257), ("powers", "bases", 1, 16385)]:
@@ -104,15 +99,7 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path):
         parts.append(struct.pack("<3Q", ("sum", "dot", "dot_shared", "powers").index(op), n, t) + b"".join(np.ascontiguousarray(x).tobytes() for x in c))
         rows += n
     blob = b"".join(parts) + struct.pack("<Q", 4)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "%d records, %d rows match" % (len(parts), rows) in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "%d records, %d rows match" % (len(parts), rows))
     bad = bytearray(blob)
     bad[-16] ^= 1                                                                       # the last record's last expected limb
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "record %d: row 0:" % (len(parts) - 1) in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "record %d: row 0:" % (len(parts) - 1))

@@ -7,19 +7,15 @@ least one check must fail, and the families `killers` names must be among the fa
 pass).  Every planted defect stays inside the memory the emulation allocates (a shared b sits at the front of a zeroed
 n x terms array there).  The unmutated copy passes, and every `old` text occurs exactly once in its header.  Nothing is written
 inside the repository tree."""
-import concurrent.futures
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import scvec_rows as R
+from tests.emul_build import CSRC
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SCVEC, ARITH = "zc_scvec.hip.h", "zc_arith.hip.h"
 
 MUTANTS = [
@@ -54,45 +50,15 @@ MUTANTS = [
 BY_NAME = {m["name"]: m for m in MUTANTS}
 
 
-def make_copy(where, m=None):
-    csrc = os.path.join(where, "dusk_zerocaf_amd", "csrc")
-    emul = os.path.join(where, "tests", "emul")
-    os.makedirs(csrc)
-    os.makedirs(emul)
-    for f in glob.glob(os.path.join(R.CSRC, "*.h")):
-        shutil.copy(f, csrc)
-    shutil.copy(os.path.join(R.EMUL_DIR, "scvec_emul.cpp"), emul)
-    if m is not None:
-        path = os.path.join(csrc, m["header"])
-        with open(path) as f:
-            text = f.read()
-        assert text.count(m["old"]) == 1, m["name"]
-        with open(path, "w") as f:
-            f.write(text.replace(m["old"], m["new"]))
-    so = os.path.join(where, "libzc_scvec.so")
-    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-DZC_CHECK_BOUNDS", "-fno-gnu-unique", "-Wl,-Bsymbolic",
-                           "-I" + R.ROCM_INC, "-o", so, os.path.join(emul, "scvec_emul.cpp")])
-    return so
-
-
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    if not os.path.isdir(R.ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    names = [None] + [m["name"] for m in MUTANTS]
-    dirs = [str(tmp_path_factory.mktemp(n or "unmutated")) for n in names]
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-        out = dict(zip(names, pool.map(lambda a: make_copy(a[0], BY_NAME.get(a[1])), zip(dirs, names))))
-    assert not any(p.startswith(ROOT + os.sep) for p in out.values())
-    return out
+    return EB.mutant_builds(tmp_path_factory, MUTANTS, "scvec_emul.cpp", flags=("-DZC_CHECK_BOUNDS",))
 
 
 def test_catalogue_is_sound():
-    assert len(BY_NAME) == len(MUTANTS) and 7 <= len(MUTANTS)
-    for m in MUTANTS:
-        text = open(os.path.join(R.CSRC, m["header"])).read()
-        assert text.count(m["old"]) == 1 and m["old"] != m["new"], m["name"]
-    scv = open(os.path.join(R.CSRC, SCVEC)).read()
+    EB.catalogue_is_sound(MUTANTS)
+    assert 7 <= len(MUTANTS)
+    scv = open(os.path.join(CSRC, SCVEC)).read()
     section = lambda a, b: scv[scv.index(a):scv.index(b)]
     assert BY_NAME["carry_pass_one_product_late"]["old"] in section("ZC_DI fe scv_slice_dot(", "ZC_DI fe scv_slice_sum(")
     assert BY_NAME["last_slice_tail_dropped"]["old"] in section("ZC_DI u32 scv_fold_steps(", "ZC_DI size_t scv_b_record(")
@@ -100,7 +66,7 @@ def test_catalogue_is_sound():
     for name in ("x_to_the_G_off_by_one", "first_power_taken_from_x"):
         assert BY_NAME[name]["old"] in section("ZC_DI void scv_pow_lane(", "// the kernels: hipcc only")
     assert BY_NAME["nineteenth_limb_dropped"]["old"] in section("ZC_DI fe scv_cols_fold(", "ZC_DI fe scv_pair(")
-    arith = open(os.path.join(R.CSRC, ARITH)).read()
+    arith = open(os.path.join(CSRC, ARITH)).read()
     assert BY_NAME["high_bits_of_a_word_not_masked"]["old"] in arith[arith.index("ZC_DI fe fe_from_limbs52("):arith.index("ZC_DI void fe_to_limbs52(")]
     # the kernels and the emulation go through the same functions
     kernels = scv[scv.index("// the kernels: hipcc only"):]
@@ -114,13 +80,4 @@ def test_unmutated_copy_passes(built):
 
 @pytest.mark.parametrize("name", [m["name"] for m in MUTANTS])
 def test_planted_defect_is_killed(built, name):
-    m = BY_NAME[name]
-    failed = R.failures(R.Emul(C.CDLL(built[name])))
-    assert failed != [], "%s survived" % name
-    families = {f.split(" [", 1)[0] for f in failed}
-    assert set(m["killers"]) <= families, (name, sorted(families))
-    assert not set(m.get("spared", [])) & families, (name, sorted(families))
-    for case in m.get("cases", []):
-        assert case in failed, (name, case, failed[:20])
-    for case in m.get("spared_cases", []):
-        assert case not in failed, (name, case)
+    EB.assert_killed(BY_NAME[name], R.failures(R.Emul(C.CDLL(built[name]))))

@@ -6,14 +6,12 @@ and both sides of every threshold."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import scvec_rows as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMUL_DIR = os.path.join(ROOT, "tests", "emul")
 ULL = C.c_ulonglong
 TERMS = sorted(set(list(range(0, 70)) + [127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 4095, 4096, 4097, 16383, 16384, 16385, 32767, 32768, 32769, 49151, 49152,
                                         49153, 65535, 65536, 65537, 262143, 262144, 262145, R.BIG_ROW, (1 << 22) - 1, 1 << 22, (1 << 22) + 1, 1 << 24, (1 << 24) + 77, (1 << 31) - 1]))
@@ -22,10 +20,9 @@ NS = [1, 2, 3, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1000]
 
 @pytest.fixture(scope="module")
 def plan():
-    so = os.path.join(EMUL_DIR, "libzc_scvec_plan.so")
-    deps = [os.path.join(EMUL_DIR, "scvec_plan_emul.cpp"), os.path.join(R.CSRC, "zc_scvec_plan.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-Wall", "-Werror", "-o", so, deps[0]])
+    so = EB.library("scvec_plan_emul.cpp", flags=EB.STRICT)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.plan_scvec_slice_len.restype = ULL
     lib.plan_scvec_slice_len.argtypes = [ULL, ULL, ULL]
@@ -54,7 +51,7 @@ def pow_plan(lib, n, terms):
 
 
 def test_plan_header_is_host_only_and_its_constants_are_the_ones_the_rows_read(plan):
-    text = open(os.path.join(R.CSRC, "zc_scvec_plan.h")).read()
+    text = open(os.path.join(EB.CSRC, "zc_scvec_plan.h")).read()
     code = re.sub(r"//[^\n]*", "", text)
     assert re.findall(r"#include\s+(\S+)", text) == ["<cstddef>", "<cstdint>"] and "__device__" not in code and "hip" not in code.lower()
     c, rc = constants(plan), R.plan_constants()

@@ -5,23 +5,17 @@ compared with tests/lincomb_rows.oracle_lincomb as a group element, the wire for
 tests/ris_lincomb_rows.oracle_ris_lincomb, both with the scalar vector tiled into every row; the identity the wire form rests on
 is also checked on oracle/pymodel.py alone."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import lincomb_rows as R
 from tests import shared_lincomb_rows as SL
 from tests import shared_scalar_rows as S
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 TERMS = [1, 2, 3, 5, 8]
 A5 = 0xA5A5A5A5A5A5A5A5
 
@@ -33,14 +27,9 @@ def vectors(t):
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
     checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_shared_lincomb%s.so" % ("_checked" if checked else ""))
-    deps = [os.path.join(EMUL_DIR, "shared_lincomb_emul.cpp")] + [os.path.join(CSRC, f) for f in (
-        "zc_shared.hip.h", "zc_shared_scalar.h", "zc_ris_batch.hip.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("shared_lincomb_emul.cpp", checked=checked)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.checked = checked
     return lib
@@ -112,11 +101,7 @@ def test_ed_form_planted_rows_are_what_they_are_planted_for(emul, oracle, t):
 
 def test_one_term_gives_the_limbs_of_the_single_scalar_form(emul, oracle):
     """terms == 1: the same table records and the same schedule as shared_table_build / shared_steps, whatever the entry bound."""
-    so = os.path.join(EMUL_DIR, "libzc_shared_scalar%s.so" % ("_checked" if emul.checked else ""))
-    if not os.path.exists(so):
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] + (["-DZC_CHECK_BOUNDS"] if emul.checked else []) +
-                              ["-I" + ROCM_INC, "-o", so, os.path.join(EMUL_DIR, "shared_scalar_emul.cpp")])
-    one = C.CDLL(so)
+    one = C.CDLL(EB.library("shared_scalar_emul.cpp", checked=emul.checked))
     P, (E, _) = SL.point_rows(oracle, 1), SL.encoding_rows(oracle, 1)
     for k in S.edge_scalars()[::5] + S.random_scalars(1):
         kk = np.array(k, dtype=np.uint64)

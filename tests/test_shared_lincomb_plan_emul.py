@@ -8,19 +8,15 @@ import ctypes as C
 import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import point_classes as PC
 from tests import shared_scalar_rows as S
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
 M52 = (1 << 52) - 1
 MAX_TERMS, MAX_STEPS = 8, 53
 SEED = S.SEED + 0x11C
@@ -28,11 +24,9 @@ SEED = S.SEED + 0x11C
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libzc_shared_lincomb_plan.so")
-    src = os.path.join(EMUL_DIR, "shared_lincomb_plan_emul.cpp")
-    deps = [src, os.path.join(CSRC, "zc_shared_scalar.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-o", so, src])
+    so = EB.library("shared_lincomb_plan_emul.cpp")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.emul_shared_lincomb_plan_words.restype = C.c_int
     lib.emul_shared_lincomb_schedule_bytes.restype = C.c_int
@@ -158,7 +152,7 @@ def test_one_term_is_the_single_scalar_schedule(emul):
 def test_the_struct_is_a_fixed_size_pod_well_under_the_kernel_arguments(emul):
     assert emul.emul_shared_lincomb_schedule_bytes() == 4 * (3 + MAX_TERMS + MAX_STEPS * MAX_TERMS) == 1740
     assert emul.emul_shared_lincomb_plan_words() == 2 * (3 + MAX_TERMS + 3 * MAX_STEPS * MAX_TERMS)
-    text = open(os.path.join(CSRC, "zc_shared_scalar.h")).read()
+    text = open(os.path.join(EB.CSRC, "zc_shared_scalar.h")).read()
     assert "static_assert(sizeof(shared_lincomb_schedule)" in text and "#include <hip" not in text
 
 
@@ -175,9 +169,7 @@ def test_the_densest_vector_fills_the_step_bound(emul):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, emul):
     """tests/emul/shared_lincomb_plan_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all on every fourth vector of
     the list; its exit status is the verdict."""
-    exe = str(tmp_path / "shared_lincomb_plan_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           "-o", exe, os.path.join(EMUL_DIR, "shared_lincomb_plan_san.cpp")])
+    exe = EB.sanitizer_program("shared_lincomb_plan_san.cpp", tmp_path)
     vecs = vectors()[::4]
     assert {len(v) for _, v in vecs} == set(range(1, 9))
     nw = emul.emul_shared_lincomb_plan_words()
@@ -186,16 +178,8 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, emul):
         flat = [x for w in vec for x in w]
         parts.append(struct.pack("<q%dQ" % len(flat), len(vec), *flat) + struct.pack("<%dq" % nw, *plan(emul, vec)["raw"]))
     blob = b"".join(parts) + struct.pack("<q", 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "%d cases match" % len(vecs) in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "%d cases match" % len(vecs))
     # the verdict is a real one: one expected word changed and the program says so
     bad = bytearray(blob)
     bad[len(parts[0]) + 8 * (1 + 5 * len(vecs[1][1]))] ^= 1                     # the step count of the second vector's first schedule
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "case 1: word 0" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "case 1: word 0")

@@ -4,36 +4,25 @@ shared_scalar_emul.cpp in the plain and the bounds-asserting (-DZC_CHECK_BOUNDS)
 (table_ptr).  Every row is compared with the C oracle (ed_scalar_mul, ris_roundtrip_mul); the k / 2 identity the wire form
 rests on is also checked on Python integers against oracle/pymodel.py, so both oracles are on record."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import hostile_rows as H
 from tests import shared_scalar_rows as S
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 SCALARS = S.edge_scalars() + S.random_scalars(8)
 
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
     checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_shared_scalar%s.so" % ("_checked" if checked else ""))
-    deps = [os.path.join(EMUL_DIR, "shared_scalar_emul.cpp")] + [os.path.join(CSRC, f) for f in (
-        "zc_shared.hip.h", "zc_shared_scalar.h", "zc_ris_batch.hip.h", "zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + ROCM_INC, "-o", so, deps[0]])
+    so = EB.library("shared_scalar_emul.cpp", checked=checked)
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.checked = checked
     return lib

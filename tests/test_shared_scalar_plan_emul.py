@@ -4,23 +4,17 @@ as the device's scalar_effective, built for the host beside it, and as the refer
 mod L) / 2 mod L, and the width-5 signed sliding-window schedule of either.  The sanitizer run is a stand-alone program
 (tests/emul/shared_scalar_plan_san.cpp) replaying a vector file as a child process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import point_classes as PC
 from tests import vectors as V
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
-CSRC = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-ROCM_INC = "/opt/rocm/include"
 M52 = (1 << 52) - 1
 MAX_STEPS = 53
 SEED = V.SEED + 0x5A4ED
@@ -55,13 +49,9 @@ def scalar_patterns():
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libzc_shared_scalar_plan.so")
-    src = os.path.join(EMUL_DIR, "shared_scalar_plan_emul.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("zc_shared_scalar.h", "zc_curve.hip.h", "zc_arith.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.isdir(ROCM_INC):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", so, src])
+    so = EB.library("shared_scalar_plan_emul.cpp")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.emul_shared_plan_words.restype = C.c_int
     return lib
@@ -155,27 +145,15 @@ def test_the_worst_case_count_of_steps(emul):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, emul):
     """tests/emul/shared_scalar_plan_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all on the whole list; its
     exit status is the verdict."""
-    if not os.path.isdir(ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "shared_scalar_plan_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-o", exe, os.path.join(EMUL_DIR, "shared_scalar_plan_san.cpp")])
+    exe = EB.sanitizer_program("shared_scalar_plan_san.cpp", tmp_path)
     pats = scalar_patterns()
     blob = b""
     for name, words in pats:
         blob += struct.pack("<q5Q", 1, *words) + struct.pack("<%dq" % emul.emul_shared_plan_words(), *plan(emul, words)["raw"])
     blob += struct.pack("<q", 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "%d cases match" % len(pats) in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "%d cases match" % len(pats))
     # the verdict is a real one: one expected word changed and the program says so
     bad = bytearray(blob)
     rec = 8 * (1 + 5 + emul.emul_shared_plan_words())
     bad[3 * rec + 8 * 6 + 8 * 15] ^= 1                                           # the step count of the fourth scalar's first schedule
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "case 3: word 15" in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "case 3: word 15")

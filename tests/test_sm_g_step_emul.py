@@ -8,19 +8,13 @@ Two host builds of the very per-lane functions the kernel calls, plain and bound
   * tests/emul/sm_g_step_emul.cpp: one lane step by step -- an addition leaves N alone, a doubling leaves Q alone, and a lane
     whose `active` is cleared, before its first step or after any later one, keeps Q, N and its state exactly."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import pymodel as pm
+from tests import emul_build as EB
 from tests import vectors as V
 from tests.test_sm_schedule_emul import model, run_tiles, tile_emul  # noqa: F401  (fixtures: the same host build)
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMUL_DIR = os.path.join(HERE, "emul")
 
 ALL_ONES_252 = (1 << 252) - 1
 ALT_10 = int("10" * 126, 2)                      # 252 bits, top bit set
@@ -98,17 +92,9 @@ def test_lanes_that_retire_mid_tile_keep_q(tile_emul, model, oracle):
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def g_step_emul(request):
-    checked = request.param == "checked"
-    so = os.path.join(EMUL_DIR, "libzc_sm_g_step%s.so" % ("_checked" if checked else ""))
-    src = os.path.join(EMUL_DIR, "sm_g_step_emul.cpp")
-    csrc = os.path.join(ROOT, "dusk_zerocaf_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("zc_arith.hip.h", "zc_curve.hip.h", "zc_constants.hip.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        inc = "/opt/rocm/include"
-        if not os.path.isdir(inc):
-            pytest.skip("ROCm headers not present")
-        subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-O2"] +
-                              (["-DZC_CHECK_BOUNDS"] if checked else []) + ["-I" + inc, "-o", so, src])
+    so = EB.library("sm_g_step_emul.cpp", checked=request.param == "checked")
+    if so is None:
+        pytest.skip("ROCm headers not present")
     lib = C.CDLL(so)
     lib.emul_g_step_keeps.restype = C.c_int
     return lib

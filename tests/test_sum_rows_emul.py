@@ -5,13 +5,12 @@ ed_add in the documented order), the wire form byte-identical to the oracle's de
 accept bits, for every term count of the GPU tier.  The sanitizer run is a stand-alone program (tests/emul/sum_rows_san.cpp)
 replaying a vector file as a child process: nothing sanitized is loaded here."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import emul_build as EB
 from tests import sum_rows as SR
 
 SHORT_N, LONG_N = 257, 3
@@ -19,7 +18,7 @@ SHORT_N, LONG_N = 257, 3
 
 @pytest.fixture(scope="module", params=["plain", "checked"])
 def emul(request):
-    so = SR.build_emul(request.param == "checked")
+    so = EB.library("sum_rows_emul.cpp", checked=request.param == "checked")
     if so is None:
         pytest.skip("ROCm headers not present")
     return SR.Emul(C.CDLL(so))
@@ -100,11 +99,7 @@ def test_the_folds_decoder_is_ris_decompress(emul, oracle):
 def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
     """tests/emul/sum_rows_san.cpp with -fsanitize=address,undefined -fno-sanitize-recover=all: inputs and outputs in heap blocks of
     exactly their size, one record per term count on either side of every plan boundary; its exit status is the verdict."""
-    if not os.path.isdir(SR.ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    exe = str(tmp_path / "sum_rows_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           "-D__HIP_PLATFORM_AMD__", "-I" + SR.ROCM_INC, "-o", exe, os.path.join(SR.EMUL_DIR, "sum_rows_san.cpp")])
+    exe = EB.sanitizer_program("sum_rows_san.cpp", tmp_path)
     blob, rows, records = b"", 0, 0
     for terms in (0, 1, 3, 32, 33, 47, 4096, 8197):
         n = 2 if terms in SR.LONG_TERMS else 9
@@ -114,15 +109,7 @@ def test_stand_alone_program_under_asan_and_ubsan(tmp_path, oracle):
         rows += n
         records += 1
     blob += struct.pack("<Q", 0)
-    good = tmp_path / "vectors.bin"
-    good.write_bytes(blob)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(good)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "%d records, %d rows match" % (records, rows) in run.stdout, (run.returncode, run.stdout[-500:], run.stderr[-3000:])
-    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    EB.assert_clean(EB.run_vectors(exe, blob, tmp_path, "vectors.bin"), "%d records, %d rows match" % (records, rows))
     bad = bytearray(blob)
     bad[-8 - 8 * 2 - 1] ^= 1                                                            # the last byte of the last expected encoding
-    wrong = tmp_path / "wrong.bin"
-    wrong.write_bytes(bytes(bad))
-    run = subprocess.run([exe, str(wrong)], capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 1 and "record %d: row 1: the encoding differs" % (records - 1) in run.stderr, (run.returncode, run.stderr[-500:])
+    EB.assert_caught(EB.run_vectors(exe, bad, tmp_path, "wrong.bin"), "record %d: row 1: the encoding differs" % (records - 1))

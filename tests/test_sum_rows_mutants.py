@@ -11,18 +11,15 @@ The fold started from the identity (identity + P_0 + ...) is the same group elem
 checks -- of every term count from 1 up, the one-term row that must be its point among them -- and nothing else; it spares the
 families "ed_eq" (group equality and compressed bytes) and "wire" (an encoding depends on the group element only), in the
 Edwards fold and in the wire fold alike.  Only limb-for-limb comparison against the model tells it apart."""
-import concurrent.futures
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
+from tests import emul_build as EB
 from tests import sum_rows as SR
+from tests.emul_build import CSRC
 
-CSRC = SR.CSRC
 SUM, PLAN = "zc_sum.hip.h", "zc_sum_plan.h"
 ALL = ["ed", "ed_eq", "wire"]
 
@@ -53,45 +50,14 @@ MUTANTS = [
 BY_NAME = {m["name"]: m for m in MUTANTS}
 
 
-def make_copy(where, m=None):
-    csrc = os.path.join(where, "dusk_zerocaf_amd", "csrc")
-    emul = os.path.join(where, "tests", "emul")
-    os.makedirs(csrc)
-    os.makedirs(emul)
-    for f in glob.glob(os.path.join(CSRC, "*.h")):
-        shutil.copy(f, csrc)
-    shutil.copy(os.path.join(SR.EMUL_DIR, "sum_rows_emul.cpp"), emul)
-    if m is not None:
-        path = os.path.join(csrc, m["header"])
-        with open(path) as f:
-            text = f.read()
-        assert text.count(m["old"]) == 1, m["name"]
-        with open(path, "w") as f:
-            f.write(text.replace(m["old"], m["new"]))
-    so = os.path.join(where, "libzc_sum_rows.so")
-    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-O2", "-D__HIP_PLATFORM_AMD__", "-fno-gnu-unique", "-Wl,-Bsymbolic",
-                           "-I" + SR.ROCM_INC, "-o", so, os.path.join(emul, "sum_rows_emul.cpp")])
-    return so
-
-
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    if not os.path.isdir(SR.ROCM_INC):
-        pytest.skip("ROCm headers not present")
-    names = [None] + [m["name"] for m in MUTANTS]
-    dirs = [str(tmp_path_factory.mktemp(n or "unmutated")) for n in names]
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-        out = dict(zip(names, pool.map(lambda a: make_copy(a[0], BY_NAME.get(a[1])), zip(dirs, names))))
-    root = os.path.dirname(SR.HERE)
-    assert not any(p.startswith(root + os.sep) for p in out.values())
-    return out
+    return EB.mutant_builds(tmp_path_factory, MUTANTS, "sum_rows_emul.cpp")
 
 
 def test_catalogue_is_sound():
-    assert len(BY_NAME) == len(MUTANTS) and 6 <= len(MUTANTS)
-    for m in MUTANTS:
-        text = open(os.path.join(CSRC, m["header"])).read()
-        assert text.count(m["old"]) == 1 and m["old"] != m["new"], m["name"]
+    EB.catalogue_is_sound(MUTANTS)
+    assert 6 <= len(MUTANTS)
     text = open(os.path.join(CSRC, SUM)).read()
     device = text[:text.index("#if defined(__HIPCC__)")]                                # what the emulation builds: the functions the kernels call
     for m in MUTANTS:
@@ -114,11 +80,4 @@ def test_planted_defect_is_killed(built, oracle, name):
     if m.get("survives"):
         assert failed == [], (name, failed)                                             # the same group element: no byte of the wire form can tell
         return
-    assert failed != [], "%s survived" % name
-    families = {f.rsplit(" [", 1)[0] for f in failed}
-    assert set(m["killers"]) <= families, (name, sorted(families))
-    assert not set(m.get("spared", [])) & families, (name, sorted(families))
-    for case in m.get("cases", []):
-        assert case in failed, (name, case, failed)
-    for case in m.get("spared_cases", []):
-        assert case not in failed, (name, case, failed)
+    EB.assert_killed(m, failed)

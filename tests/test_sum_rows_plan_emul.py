@@ -7,15 +7,16 @@ import re
 
 import pytest
 
+from tests import emul_build as EB
 from tests import sum_rows as SR
+from tests.emul_build import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUP, TWO = 0, 1
 
 
 @pytest.fixture(scope="module")
 def emul():
-    so = SR.build_emul(False)
+    so = EB.library("sum_rows_emul.cpp")
     if so is None:
         pytest.skip("ROCm headers not present")
     return SR.Emul(C.CDLL(so))
